@@ -256,7 +256,10 @@ class TurnTransport:
 
     def ensure_permission(self, peer: Tuple[str, int]) -> None:
         now = time.monotonic()
-        if self._permitted.get(peer[0], 0) < now - 240:  # perms last 5 min
+        last = self._permitted.get(peer[0])
+        # never-permitted is its own case: the monotonic clock may read less
+        # than 240 s (fresh boot), so 0 is no stand-in for "long ago"
+        if last is None or last < now - 240:  # perms last 5 min
             self._permitted[peer[0]] = now
             self._transport.sendto(self.client.permission_request(peer),
                                    self.server)

@@ -27,7 +27,7 @@ def last_json_line(out: str) -> dict:
 def test_bench_single_process():
     env = dict(os.environ, AIRTC_BENCH_FAMILY="tiny")
     r = subprocess.run(
-        [sys.executable, BENCH, "--steps", "2", "--warmup", "1",
+        [sys.executable, BENCH, "--full", "--steps", "2", "--warmup", "1",
          "--width", "64", "--latency-frames", "2"],
         capture_output=True, text=True, timeout=280, cwd=ROOT, env=env,
     )
@@ -40,6 +40,38 @@ def test_bench_single_process():
     assert d["n_gpus"] == 1 and d["steps"] == 2
     assert d["scaling"] == "weak" and d["higher_is_better"] is True
     assert d["value"] > 0 and d["ms_per_step"] > 0
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run (no --full) prints the headline fields only, and
+    --dump-outputs writes the last timed step's frame as float32 .npy —
+    identical from run to run with the same arguments."""
+    import numpy as np
+
+    env = dict(os.environ, AIRTC_BENCH_FAMILY="tiny")
+    dumps = []
+    for sub in ("a", "b"):
+        out_dir = tmp_path / sub
+        r = subprocess.run(
+            [sys.executable, BENCH, "--gpus", "1", "--steps=3", "--warmup", "1",
+             "--width", "64", "--dump-outputs", str(out_dir)],
+            capture_output=True, text=True, timeout=140, cwd=ROOT, env=env,
+        )
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = last_json_line(r.stdout)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype",
+                    "ms_per_step"):
+            assert key in d, f"missing {key}"
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        # the latency samples live behind --full
+        assert "p50_engine_ms" not in d and "p50_glass_to_glass_ms" not in d
+        assert sorted(p.name for p in out_dir.iterdir()) == ["output.npy"]
+        arr = np.load(out_dir / "output.npy")
+        assert arr.dtype == np.float32 and arr.shape == (64, 64, 3)
+        assert arr.min() >= 0 and arr.max() <= 255 and arr.std() > 0
+        dumps.append(arr)
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 def _free_port():

@@ -172,6 +172,30 @@ def test_sans_io_allocate_challenge_flow():
     assert cli.lifetime == 300
 
 
+def test_first_permission_requested_on_fresh_clock(monkeypatch):
+    """The first send to a peer must create its permission whatever the
+    monotonic clock reads — it can be a few seconds on a fresh boot."""
+    from ai_rtc_agent_amd.media import turn
+
+    class _Sock:
+        def __init__(self):
+            self.sent = []
+
+        def sendto(self, data, addr):
+            self.sent.append(StunMessage.parse(data).msg_type)
+
+    cli = TurnClient(USER, PASS)
+    cli.realm, cli.nonce = REALM, NONCE
+    tt = TurnTransport(cli, ("127.0.0.1", 3478), lambda d, p: None)
+    tt._transport = sock = _Sock()
+    monkeypatch.setattr(turn.time, "monotonic", lambda: 5.0)
+    tt.sendto(b"x", ("127.0.0.1", 4000))
+    tt.sendto(b"y", ("127.0.0.1", 4000))
+    perm = _mtype(M_CREATE_PERMISSION, 0)
+    send = _mtype(M_SEND, CLASS_INDICATION)
+    assert sock.sent == [perm, send, send]
+
+
 def test_transport_allocate_and_relay_roundtrip():
     async def body():
         loop = asyncio.get_event_loop()
