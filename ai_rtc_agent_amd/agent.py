@@ -9,7 +9,7 @@ Route table (reference agent.py:466-472):
     GET  /stats          FPS + per-stage latency (ours; SURVEY.md §5.5 gap)
 
 CLI flags mirror reference agent.py:441-455: --model-id --port --udp-ports
---log-level (+ MI355X extras: --gpus, --family, --resolution).
+--log-level (+ MI355X extras: --gpus, --family, --resolution, --fit).
 
 Session model: connection handling is identical to the reference at the
 signalling level; the media transport underneath is our ICE-lite RTP stack
@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import argparse
 import logging
+import os
 import uuid
 from typing import Optional
 
@@ -264,6 +265,8 @@ async def on_startup(app: web.Application) -> None:
             width=app.get("resolution", 512),
             height=app.get("resolution", 512),
         )
+        if app.get("fit_mode"):
+            cfg.fit_mode = app["fit_mode"]
         st["pool"] = PipelinePool.create(
             model_id=app["model_id"], n_gpus=app["n_gpus"], cfg=cfg,
             streams_per_replica=app.get("streams_per_gpu", 1),
@@ -302,6 +305,7 @@ def create_app(
     family: str = "sd15",
     resolution: int = 512,
     streams_per_gpu: int = 1,
+    fit_mode: Optional[str] = None,
 ) -> web.Application:
     app = web.Application(middlewares=[cors_middleware])
     app["model_id"] = model_id
@@ -312,6 +316,7 @@ def create_app(
     app["family"] = family
     app["resolution"] = resolution
     app["streams_per_gpu"] = streams_per_gpu
+    app["fit_mode"] = fit_mode  # None: EngineConfig default (AIRTC_FIT_MODE)
     app["state"] = {
         "pcs": set(),
         "source_track": None,
@@ -347,6 +352,14 @@ def main() -> None:
     parser.add_argument("--family", default="sd15", choices=["sd15", "sd21", "sdxl"],
                         help="UNet family served by the pipeline")
     parser.add_argument("--resolution", type=int, default=512)
+    parser.add_argument("--fit", default=None,
+                        choices=["cover", "contain", "stretch"],
+                        help="how frames of another size are fitted to "
+                             "--resolution on the GPU: cover = centred crop "
+                             "to the engine aspect then resize (default), "
+                             "contain = whole frame with black bars, "
+                             "stretch = whole frame, aspect not kept "
+                             "(default: $AIRTC_FIT_MODE or cover)")
     parser.add_argument("--streams-per-gpu", type=int, default=1,
                         help="multi-stream batched serving: sessions per "
                              "GPU batched through one engine (fbs=K; "
@@ -371,6 +384,10 @@ def main() -> None:
 
         from .parallel.frontend import WorkerFrontend
 
+        if args.fit:
+            # workers are spawned processes: they inherit the environment
+            # and EngineConfig.fit_mode defaults from it
+            os.environ["AIRTC_FIT_MODE"] = args.fit
         fe = WorkerFrontend(args.workers, model_id=args.model_id,
                             family=args.family, resolution=args.resolution,
                             pin_gpu=torch.cuda.is_available(),
@@ -384,7 +401,7 @@ def main() -> None:
         return
     app = create_app(model_id=args.model_id, udp_ports=ports, n_gpus=args.gpus,
                      family=args.family, resolution=args.resolution,
-                     streams_per_gpu=args.streams_per_gpu)
+                     streams_per_gpu=args.streams_per_gpu, fit_mode=args.fit)
     web.run_app(app, host=args.host, port=args.port)
 
 

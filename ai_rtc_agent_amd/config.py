@@ -43,6 +43,8 @@ def _env_float(name: str, default: float) -> float:
 # VCN_ENC_PRESET / VCN_ENC_TUNING_INFO / VCN_ENC_{DEFAULT,MIN,MAX}_BITRATE
 #                                     -> encoder tunables (5-knob parity with
 #                                        NVENC_* in reference docs/environment.md:17-25)
+# AIRTC_FIT_MODE (cover|contain|stretch) -> EngineConfig.fit_mode, how frames
+#                                        of another resolution are fitted
 
 
 def engines_cache_dir() -> str:
@@ -149,6 +151,13 @@ class EngineConfig:
     fp8_calib_frames: int = field(default_factory=lambda: _env_int("AIRTC_FP8_CALIB_FRAMES", 8))
     fp8_margin: float = field(default_factory=lambda: _env_float("AIRTC_FP8_MARGIN", 1.5))
     fp8_min_snr_db: float = field(default_factory=lambda: _env_float("AIRTC_FP8_MIN_SNR_DB", 16.0))
+
+    # any-resolution ingest: how a frame whose size is not (height, width)
+    # is fitted into the engine's input slot on the device
+    # (ops.fit_frame_u8): cover = centred crop to the engine aspect, then
+    # resize; contain = whole frame with black bars; stretch = whole frame,
+    # aspect not kept. Engine-sized frames are never touched.
+    fit_mode: str = field(default_factory=lambda: os.environ.get("AIRTC_FIT_MODE") or "cover")
 
     @property
     def denoising_steps(self) -> int:

@@ -249,6 +249,10 @@ class StreamDiffusionEngine:
         # static I/O buffers (graph-stable addresses); _frame_in (u8) is the
         # only per-frame input — preprocess lives inside the graph
         self._frame_in = torch.zeros((fbs, cfg.height, cfg.width, 3), device=dev, dtype=torch.uint8)
+        if cfg.fit_mode not in ops.FIT_MODES:
+            raise ValueError(f"fit_mode must be one of {ops.FIT_MODES}, got {cfg.fit_mode!r}")
+        # last source (height, width) seen per slot — stats()["ingest"]
+        self._src_size: list = [None] * fbs
         self._ts_batch = self._coeff["sub_timesteps_tensor"].to(dev)
         self._prev_out: Optional[torch.Tensor] = None
         self._graph = None
@@ -696,17 +700,93 @@ class StreamDiffusionEngine:
     # ------------------------------------------------------------------
     # public frame API
     # ------------------------------------------------------------------
+    def _fit_into(self, srcs, out: torch.Tensor) -> None:
+        """Write every slot of `out` (fbs, H, W, 3) from its source frame on
+        the current stream: engine-sized sources are copied, any other size
+        goes through the fused crop+resize kernel (ops.fit_frame_u8)."""
+        shape = out.shape[1:]
+        for b, src in enumerate(srcs):
+            if src.shape == shape:
+                out[b].copy_(src)
+            else:
+                ops.fit_frame_u8(src, out, b, self.cfg.fit_mode)
+
+    def _load_frame_in(self, frame_u8, srcs, stream=None) -> None:
+        """Fill the static input slot on the current stream. `srcs` is None
+        on the equal-size path (one plain copy, as ever). Otherwise it holds
+        one device frame per slot and each is fitted STRAIGHT INTO
+        _frame_in[b] by the stream that owns _frame_in. In pipelined mode
+        that is stream A, after its wait on _ev_in (upload finished) and
+        _ev_done (previous replays done), so the fit is ordered against the
+        g1 replay that reads the slot exactly as the plain copy is. There is
+        deliberately no staging buffer on the caller's stream: the caller
+        runs ahead of stream A, and frame i+1's fit would overwrite a shared
+        staging buffer before stream A had consumed frame i. The sources
+        were allocated on the caller's stream, hence record_stream."""
+        if srcs is None:
+            self._frame_in.copy_(frame_u8)
+            if stream is not None:
+                frame_u8.record_stream(stream)
+            return
+        self._fit_into(srcs, self._frame_in)
+        if stream is not None:
+            for src in srcs:
+                src.record_stream(stream)
+
     @torch.no_grad()
-    def __call__(self, frame_u8: torch.Tensor) -> torch.Tensor:
-        """frame_u8: (H,W,3) or (fbs,H,W,3) uint8 RGB on any device.
+    def __call__(self, frame_u8) -> torch.Tensor:
+        """frame_u8: (H,W,3) or (fbs,H,W,3) uint8 RGB on any device, or a
+        list/tuple of fbs (Hs,Ws,3) frames of differing sizes. Frames whose
+        size is not the engine's (cfg.height, cfg.width) are uploaded at
+        source size and fitted on the device (cfg.fit_mode).
         Returns stylised (H,W,3) / (fbs,H,W,3) uint8 RGB on self.device."""
         assert self._prepared, "call prepare() first"
-        squeeze = frame_u8.dim() == 3
-        if squeeze:
-            frame_u8 = frame_u8.unsqueeze(0)
+        cfg = self.cfg
+        eng_shape = (cfg.height, cfg.width, 3)
+        # srcs: per-slot source frames when any of them needs fitting;
+        # None = everything is engine-sized (the path is what it always was)
+        srcs = None
+        if isinstance(frame_u8, (list, tuple)):
+            squeeze = False
+            if len(frame_u8) != cfg.frame_buffer_size:
+                raise ValueError(
+                    f"expected {cfg.frame_buffer_size} frames, got {len(frame_u8)}")
+            if all(tuple(t.shape) == eng_shape for t in frame_u8):
+                frame_u8 = torch.stack(
+                    [t.to(self.device, non_blocking=True) for t in frame_u8])
+            else:
+                srcs = list(frame_u8)
+        else:
+            squeeze = frame_u8.dim() == 3
+            if squeeze:
+                frame_u8 = frame_u8.unsqueeze(0)
+            if tuple(frame_u8.shape[1:]) != eng_shape:
+                if frame_u8.shape[0] != cfg.frame_buffer_size:
+                    raise ValueError(
+                        f"expected {cfg.frame_buffer_size} frames, got {frame_u8.shape[0]}")
+                srcs = list(frame_u8.unbind(0))
 
         with self.timers.stage("preprocess"):
-            frame_u8 = frame_u8.to(self.device, non_blocking=True)
+            if srcs is None:
+                frame_u8 = frame_u8.to(self.device, non_blocking=True)
+                self._src_size = [eng_shape[:2]] * frame_u8.shape[0]
+            else:
+                for t in srcs:
+                    if t.dim() != 3 or t.shape[-1] != 3 or t.dtype != torch.uint8:
+                        raise ValueError(
+                            f"frames must be (Hs,Ws,3) uint8, got {tuple(t.shape)} {t.dtype}")
+                srcs = [t.to(self.device, non_blocking=True) for t in srcs]
+                self._src_size = [(int(t.shape[0]), int(t.shape[1])) for t in srcs]
+                if self.sim_filter is not None:
+                    # the filter must see the FITTED frame (its signature
+                    # then never depends on the source resolution) and it
+                    # decides before stream A is touched: fit into a fresh
+                    # per-call tensor on the caller's stream and continue
+                    # on the equal-size path (no shared staging: each call
+                    # owns its tensor, record_stream covers stream A)
+                    frame_u8 = torch.empty_like(self._frame_in)
+                    self._fit_into(srcs, frame_u8)
+                    srcs = None
 
         if self.sim_filter is not None and self._prev_out is not None:
             # on-device pooled cosine (centering + 64x64 avg-pool inside
@@ -729,8 +809,7 @@ class StreamDiffusionEngine:
                     with torch.cuda.stream(self._sA):
                         self._sA.wait_event(self._ev_in)
                         self._sA.wait_event(self._ev_done[pp])
-                        self._frame_in.copy_(frame_u8)
-                        frame_u8.record_stream(self._sA)
+                        self._load_frame_in(frame_u8, srcs, self._sA)
                         self._g1[pp].replay()
                         self._ev_lat[pp].record()
                     with torch.cuda.stream(self._sB):
@@ -740,11 +819,11 @@ class StreamDiffusionEngine:
                     self._last_done = self._ev_done[pp]
                     out = self._out_u8[pp]
                 else:
-                    self._frame_in.copy_(frame_u8)
+                    self._load_frame_in(frame_u8, srcs)
                     self._graph.replay()
                     out = self._graph_out
             else:
-                self._frame_in.copy_(frame_u8)
+                self._load_frame_in(frame_u8, srcs)
                 out = self._step_core()
                 if self._fp8_calib_left:
                     self._fp8_calib_left -= 1
@@ -772,6 +851,15 @@ class StreamDiffusionEngine:
 
     def stats(self) -> dict:
         d = self.timers.snapshot()
+        d["ingest"] = {
+            "fit_mode": self.cfg.fit_mode,
+            "engine_size": [self.cfg.height, self.cfg.width],
+            # last source [height, width] per slot (None: no frame yet)
+            "last_source_size": [
+                None if sz is None else list(sz)
+                for sz in getattr(self, "_src_size", [])
+            ],
+        }
         if self.cfg.use_fp8:
             d["fp8"] = {
                 "active": self.fp8_active,

@@ -254,3 +254,157 @@ extern "C" void airtc_sched_blend(const uint16_t* xt, const uint16_t* eps,
                      reinterpret_cast<const f16*>(eps), a, bt, c_out, c_skip,
                      reinterpret_cast<f16*>(out), per_b / 8, n8);
 }
+
+// ---------------------------------------------------------------------------
+// fit_resize_u8: any-resolution ingest. One launch crops a source window
+// (y0, x0, ch, cw) out of a u8 RGB NHWC frame, resizes it with the separable
+// antialiased triangle filter (the filter of F.interpolate(mode="bilinear",
+// antialias=True, align_corners=False)) into the destination window
+// (oy, ox, oh, ow) of ONE (H, W, 3) u8 slot, and writes 0 everywhere else in
+// that slot (the `contain` bars). Per axis, scale = n_in/n_out,
+// sup = max(scale, 1), centre c = (o+0.5)*scale, taps
+// [max(int(c-sup+0.5), 0), min(int(c+sup+0.5), n_in)), weight
+// max(0, 1-|(j-c+0.5)/sup|) normalised to sum 1; taps clamp to the WINDOW.
+//
+// Shape: a workgroup owns a destination tile of FIT_TH rows x FIT_TW pixels
+// and one lane owns one channel column of it (FIT_COLS = 3*FIT_TW lanes, so
+// LDS reads/writes and the u8 stores are lane-consecutive). The source rows
+// the tile needs are consumed in chunks of FIT_ROWS: horizontal pass
+// global u8 -> f32 LDS (4 rows per step so 4 loads are in flight per tap),
+// then the vertical pass accumulates that chunk's contribution out of LDS
+// into FIT_TH f32 registers. Tap loops and the chunk loop are sized from
+// the scale at run time, so LDS is fixed (24 KB) and NO downscale factor
+// truncates taps. Source access is byte-wise: no pitch/alignment
+// assumptions (Ws*3 need not be a multiple of 4).
+// ---------------------------------------------------------------------------
+#define FIT_TW 64
+#define FIT_TH 8
+#define FIT_COLS (FIT_TW * 3)
+#define FIT_ROWS 32
+
+__device__ __forceinline__ void fit_taps(int o, double scale, double sup,
+                                         int n_in, int& start, int& end,
+                                         double& c) {
+  c = (o + 0.5) * scale;
+  start = max((int)(c - sup + 0.5), 0);
+  end = min((int)(c + sup + 0.5), n_in);
+}
+
+__device__ __forceinline__ float fit_weight(float d, float inv_sup) {
+  return fmaxf(0.0f, 1.0f - fabsf(d * inv_sup));
+}
+
+__global__ __launch_bounds__(FIT_COLS) void fit_resize_u8_kernel(
+    const uint8_t* __restrict__ src, long spitch, uint8_t* __restrict__ dst,
+    int H, int W, int y0, int x0, int ch, int cw, int oy, int ox, int oh,
+    int ow) {
+  __shared__ float rows[FIT_ROWS * FIT_COLS];
+  const int tid = threadIdx.x;
+  const int col = blockIdx.x * FIT_COLS + tid;  // dst channel column
+  const int px = col / 3, chn = col - px * 3;
+  const int ty0 = blockIdx.y * FIT_TH;
+  const bool col_ok = col < W * 3;
+  const bool in_x = col_ok && px >= ox && px < ox + ow;
+
+  const double sx = (double)cw / ow, sy = (double)ch / oh;
+  const double supx = fmax(sx, 1.0), supy = fmax(sy, 1.0);
+  const float isupx = (float)(1.0 / supx), isupy = (float)(1.0 / supy);
+
+  // horizontal taps of this lane's pixel: xs.., xn taps, fx = xs-c+0.5
+  int xs = 0, xn = 0;
+  float fx = 0.0f, inv_nx = 0.0f;
+  if (in_x) {
+    int xe;
+    double c;
+    fit_taps(px - ox, sx, supx, cw, xs, xe, c);
+    xn = xe - xs;
+    fx = (float)(xs - c + 0.5);
+    float sum = 0.0f;
+    for (int k = 0; k < xn; ++k) sum += fit_weight(fx + k, isupx);
+    inv_nx = 1.0f / sum;
+  }
+
+  // vertical taps of the tile's rows (block-uniform); rows outside the
+  // destination window keep zero taps and are written as 0
+  int ys[FIT_TH], ye[FIT_TH];
+  float dy[FIT_TH], inv_ny[FIT_TH], acc[FIT_TH];
+  int ylo = 0, yhi = 0;
+  bool any = false;
+#pragma unroll
+  for (int t = 0; t < FIT_TH; ++t) {
+    const int o = ty0 + t - oy;
+    ys[t] = ye[t] = 0;
+    dy[t] = inv_ny[t] = acc[t] = 0.0f;
+    if (o >= 0 && o < oh) {
+      double c;
+      fit_taps(o, sy, supy, ch, ys[t], ye[t], c);
+      if (!any) ylo = ys[t];
+      any = true;
+      yhi = ye[t];
+      // weight argument (j - c + 0.5) == (j - ylo) - dy
+      dy[t] = (float)(c - 0.5 - ylo);
+      float sum = 0.0f;
+      for (int r = ys[t]; r < ye[t]; ++r)
+        sum += fit_weight((float)(r - ylo) - dy[t], isupy);
+      inv_ny[t] = 1.0f / sum;
+    }
+  }
+
+  for (int r0 = ylo; r0 < yhi; r0 += FIT_ROWS) {
+    const int nr = min(FIT_ROWS, yhi - r0);
+    if (in_x) {
+      const uint8_t* base =
+          src + (long)(y0 + r0) * spitch + (long)(x0 + xs) * 3 + chn;
+      for (int r = 0; r < nr; r += 4) {
+        // rows past the chunk re-read its last row (in bounds, discarded)
+        const uint8_t* p0 = base + (long)r * spitch;
+        const uint8_t* p1 = base + (long)min(r + 1, nr - 1) * spitch;
+        const uint8_t* p2 = base + (long)min(r + 2, nr - 1) * spitch;
+        const uint8_t* p3 = base + (long)min(r + 3, nr - 1) * spitch;
+        float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+        for (int k = 0; k < xn; ++k) {
+          const float w = fit_weight(fx + k, isupx);
+          a0 += w * (float)p0[k * 3];
+          a1 += w * (float)p1[k * 3];
+          a2 += w * (float)p2[k * 3];
+          a3 += w * (float)p3[k * 3];
+        }
+        // FIT_ROWS % 4 == 0: r+3 stays inside the LDS tile
+        rows[(r + 0) * FIT_COLS + tid] = a0 * inv_nx;
+        rows[(r + 1) * FIT_COLS + tid] = a1 * inv_nx;
+        rows[(r + 2) * FIT_COLS + tid] = a2 * inv_nx;
+        rows[(r + 3) * FIT_COLS + tid] = a3 * inv_nx;
+      }
+    }
+    __syncthreads();
+    if (in_x) {
+#pragma unroll
+      for (int t = 0; t < FIT_TH; ++t) {
+        const int a = max(ys[t], r0), b = min(ye[t], r0 + nr);
+        for (int r = a; r < b; ++r)
+          acc[t] += fit_weight((float)(r - ylo) - dy[t], isupy) *
+                    rows[(r - r0) * FIT_COLS + tid];
+      }
+    }
+    __syncthreads();
+  }
+
+  if (!col_ok) return;
+#pragma unroll
+  for (int t = 0; t < FIT_TH; ++t) {
+    const int y = ty0 + t;
+    if (y >= H) break;
+    float v = in_x ? nearbyintf(acc[t] * inv_ny[t]) : 0.0f;
+    v = fminf(255.0f, fmaxf(0.0f, v));
+    dst[(long)y * W * 3 + col] = (uint8_t)v;
+  }
+}
+
+extern "C" void airtc_fit_resize_u8(const uint8_t* src, int Ws, uint8_t* dst,
+                                    int H, int W, int y0, int x0, int ch,
+                                    int cw, int oy, int ox, int oh, int ow,
+                                    hipStream_t s) {
+  dim3 grid((W * 3 + FIT_COLS - 1) / FIT_COLS, (H + FIT_TH - 1) / FIT_TH);
+  hipLaunchKernelGGL(fit_resize_u8_kernel, grid, dim3(FIT_COLS), 0, s, src,
+                     (long)Ws * 3, dst, H, W, y0, x0, ch, cw, oy, ox, oh, ow);
+}

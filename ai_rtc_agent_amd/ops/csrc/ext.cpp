@@ -239,6 +239,34 @@ torch::Tensor postprocess_u8(torch::Tensor img) {
   return out;
 }
 
+void fit_resize_u8(torch::Tensor src, torch::Tensor dst, int64_t slot,
+                   int64_t y0, int64_t x0, int64_t ch, int64_t cw, int64_t oy,
+                   int64_t ox, int64_t oh, int64_t ow) {
+  CHECK_IN(src);
+  CHECK_IN(dst);
+  TORCH_CHECK(src.dtype() == torch::kUInt8 && dst.dtype() == torch::kUInt8);
+  TORCH_CHECK(src.device() == dst.device(), "src/dst on different devices");
+  TORCH_CHECK(src.dim() == 3 && src.size(2) == 3, "src must be (Hs, Ws, 3)");
+  TORCH_CHECK(dst.dim() == 4 && dst.size(3) == 3, "dst must be (B, H, W, 3)");
+  const int64_t Hs = src.size(0), Ws = src.size(1);
+  const int64_t B = dst.size(0), H = dst.size(1), W = dst.size(2);
+  TORCH_CHECK(Hs >= 1 && Ws >= 1 && H >= 1 && W >= 1, "empty frame");
+  TORCH_CHECK(Hs * Ws * 3 < (1LL << 31) && H * W * 3 < (1LL << 31),
+              "frame too large");
+  TORCH_CHECK(slot >= 0 && slot < B, "slot out of range");
+  // the kernel trusts these windows for every load and store
+  TORCH_CHECK(ch >= 1 && cw >= 1 && y0 >= 0 && x0 >= 0 && y0 + ch <= Hs &&
+                  x0 + cw <= Ws,
+              "source window out of range");
+  TORCH_CHECK(oh >= 1 && ow >= 1 && oy >= 0 && ox >= 0 && oy + oh <= H &&
+                  ox + ow <= W,
+              "destination window out of range");
+  airtc_fit_resize_u8(src.data_ptr<uint8_t>(), (int)Ws,
+                      dst.data_ptr<uint8_t>() + slot * H * W * 3, (int)H,
+                      (int)W, (int)y0, (int)x0, (int)ch, (int)cw, (int)oy,
+                      (int)ox, (int)oh, (int)ow, cur_stream());
+}
+
 // --- software H.264 baseline-intra codec (h264sw.cpp) -----------------
 extern "C" {
 void* airtc_h264enc_create(int w, int h);
@@ -577,6 +605,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused LCM step: c_out*(x_t - b*eps)/a + c_skip*x_t");
   m.def("preprocess_u8", &preprocess_u8);
   m.def("postprocess_u8", &postprocess_u8);
+  m.def("fit_resize_u8", &fit_resize_u8,
+        "crop + antialiased resize of a u8 RGB frame into one slot");
   m.def("conv2d_fp8", &conv2d_fp8,
         "fp8 e4m3 implicit-GEMM conv2d on the MX-scaled MFMA (NHWC)",
         pybind11::arg("x"), pybind11::arg("w_fp8"), pybind11::arg("dq"),

@@ -18,6 +18,13 @@ void airtc_add_act_f16(const uint16_t* a, const uint16_t* b, uint16_t* out,
                        long n, int act, hipStream_t s);
 void airtc_upsample2x_f16(const uint16_t* in, uint16_t* out, int B, int H,
                           int W, int C, hipStream_t s);
+// any-resolution ingest: crop src window (y0,x0,ch,cw) of a u8 RGB (Hs,Ws,3)
+// frame, antialiased-triangle resize into window (oy,ox,oh,ow) of ONE
+// (H,W,3) u8 slot `dst`, zeros elsewhere in the slot. Windows are validated
+// by the caller (ext.cpp).
+void airtc_fit_resize_u8(const uint8_t* src, int Ws, uint8_t* dst, int H,
+                         int W, int y0, int x0, int ch, int cw, int oy,
+                         int ox, int oh, int ow, hipStream_t s);
 // fused LCM scheduler math (one kernel each; coefficients are per-batch-row
 // f32 arrays of B entries, per_b = elements per batch row)
 void airtc_sched_add_noise(const uint16_t* x0, const uint16_t* noise,

@@ -582,6 +582,94 @@ def preprocess_from_u8(frame_u8: torch.Tensor, dtype: torch.dtype) -> torch.Tens
     return (frame_u8.to(torch.float32) / 127.5 - 1.0).to(dtype)
 
 
+FIT_MODES = ("cover", "contain", "stretch")
+
+
+def _round_div(a: int, b: int, c: int) -> int:
+    """round(a*b/c) in integers, clamped to >= 1."""
+    return max(1, (a * b + c // 2) // c)
+
+
+def fit_geometry(Hs: int, Ws: int, H: int, W: int, mode: str = "cover"):
+    """Integer fit geometry for a (Hs, Ws) source into a (H, W) destination.
+
+    Returns ((y0, x0, ch, cw), (oy, ox, oh, ow)): the source window that is
+    read and the destination window it is resized into.
+      cover   — largest centred source window with the destination's aspect
+                ratio; fills the whole destination (edges are cropped)
+      contain — whole source into the largest centred destination rectangle
+                with the source's aspect ratio (the rest is black bars)
+      stretch — whole source into whole destination (aspect not kept)
+    """
+    if min(Hs, Ws, H, W) < 1:
+        raise ValueError(f"empty frame: {(Hs, Ws)} -> {(H, W)}")
+    if mode == "cover":
+        if Ws * H > Hs * W:
+            ch, cw = Hs, min(Ws, _round_div(Hs, W, H))
+        else:
+            ch, cw = min(Hs, _round_div(Ws, H, W)), Ws
+        return ((Hs - ch) // 2, (Ws - cw) // 2, ch, cw), (0, 0, H, W)
+    if mode == "contain":
+        if Ws * H > Hs * W:
+            oh, ow = min(H, _round_div(W, Hs, Ws)), W
+        else:
+            oh, ow = H, min(W, _round_div(H, Ws, Hs))
+        return (0, 0, Hs, Ws), ((H - oh) // 2, (W - ow) // 2, oh, ow)
+    if mode == "stretch":
+        return (0, 0, Hs, Ws), (0, 0, H, W)
+    raise ValueError(f"fit mode must be one of {FIT_MODES}, got {mode!r}")
+
+
+def fit_frame_u8(src: torch.Tensor, out: torch.Tensor, slot: int,
+                 mode: str = "cover") -> None:
+    """Fit a u8 RGB frame of ANY size into one slot of a frame buffer.
+
+    src: (Hs, Ws, 3) u8; out: (B, H, W, 3) u8 contiguous, same device. Only
+    out[slot] is written: the fitted picture inside the destination window
+    of fit_geometry(), zeros outside it. "Crop the source window, then
+    resize it" with the separable antialiased triangle filter
+    (F.interpolate(mode="bilinear", antialias=True, align_corners=False)),
+    f32 accumulation, round-half-even, clamp to [0, 255]; equal-size
+    windows are an exact copy.
+
+    GPU: ONE launch of fit_resize_u8 (ops/csrc/elementwise.hip) on the
+    current stream, writing straight into the slot. Its tap loops and LDS
+    row chunks are sized from the scale at run time, so every downscale
+    factor runs on the kernel — nothing is routed to torch on the GPU and
+    no tap is ever truncated. CPU tensors and AIRTC_FORCE_EAGER=1 take the
+    torch reference below.
+    """
+    if src.dtype != torch.uint8 or out.dtype != torch.uint8:
+        raise TypeError("fit_frame_u8 takes uint8 tensors")
+    if src.dim() != 3 or src.shape[-1] != 3 or out.dim() != 4 or out.shape[-1] != 3:
+        raise ValueError(
+            f"fit_frame_u8 needs src (Hs,Ws,3) and out (B,H,W,3), got "
+            f"{tuple(src.shape)} and {tuple(out.shape)}")
+    if src.device != out.device:
+        raise ValueError(f"src on {src.device} but out on {out.device}")
+    if not 0 <= slot < out.shape[0]:
+        raise IndexError(f"slot {slot} out of range for {out.shape[0]} slots")
+    H, W = out.shape[1], out.shape[2]
+    (y0, x0, ch, cw), (oy, ox, oh, ow) = fit_geometry(
+        src.shape[0], src.shape[1], H, W, mode)
+    if src.is_cuda and os.environ.get("AIRTC_FORCE_EAGER") != "1":
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous (it is written in place)")
+        _require_ext().fit_resize_u8(src.contiguous(), out, slot, y0, x0, ch,
+                                     cw, oy, ox, oh, ow)
+        return
+    win = src[y0:y0 + ch, x0:x0 + cw]
+    if (ch, cw) != (oh, ow):
+        x = win.permute(2, 0, 1).unsqueeze(0).to(torch.float32)
+        x = F.interpolate(x, size=(oh, ow), mode="bilinear", antialias=True,
+                          align_corners=False)
+        win = x.round().clamp(0, 255).to(torch.uint8)[0].permute(1, 2, 0)
+    dst = out[slot]
+    if (oh, ow) != (H, W):
+        dst.zero_()
+    dst[oy:oy + oh, ox:ox + ow].copy_(win)
+
+
 def postprocess_to_u8(img: torch.Tensor) -> torch.Tensor:
     """dtype (B,H,W,3) in [-1,1] -> u8 (B,H,W,3). Reference lib/pipeline.py:72-74."""
     if _use_hip(img):

@@ -131,7 +131,14 @@ class BatchedPipeline:
                         self._frame[i] = None
                 # frames may live on mixed devices (decoder output is CPU,
                 # the engine uploads); normalise before stacking
-                batch = torch.stack([t.cpu() for t in last])
+                if all(t.shape == zeros.shape for t in last):
+                    batch = torch.stack([t.cpu() for t in last])
+                else:
+                    # sessions publish at their own resolutions: hand the
+                    # per-slot frames through, the engine fits each one on
+                    # the device (a slot with no frame yet keeps its
+                    # engine-shaped zeros)
+                    batch = [t.cpu() for t in last]
                 try:
                     out = self.base(batch)  # (K, H, W, 3)
                 except Exception as e:  # engine fault: fail the waiters,
