@@ -156,7 +156,10 @@ class Conv2d(nn.Module):
         channel_bias: torch.Tensor | None = None,
         in_affine: torch.Tensor | None = None,
         in_act: int = 0,
+        stats_groups: int | None = None,
     ) -> torch.Tensor:
+        # stats_groups: group count of the GroupNorm that reads this output
+        # directly (ops.conv2d_nhwc) — the f16 split-K path only
         act_r = act if act is not None else (ops.ACT_SILU if fuse_silu else ops.ACT_NONE)
         a_scale = None
         if x.dtype == torch.uint8:
@@ -180,7 +183,7 @@ class Conv2d(nn.Module):
         y = ops.conv2d_nhwc(
             x, self.weight, self.bias, self.stride, self.padding, fuse_silu,
             act=act, residual=residual, channel_bias=channel_bias,
-            in_affine=in_affine, in_act=in_act,
+            in_affine=in_affine, in_act=in_act, stats_groups=stats_groups,
         )
         if self._fp8_calibrate:
             self._fp8_in_amax = max(self._fp8_in_amax,
@@ -403,7 +406,12 @@ class ResnetBlock(nn.Module):
         self.shortcut = Conv2d(cin, cout, 1) if cin != cout else None
 
     def forward(self, x: torch.Tensor, temb: torch.Tensor,
-                temb_b: torch.Tensor | None = None) -> torch.Tensor:
+                temb_b: torch.Tensor | None = None,
+                next_groups: int | None = None) -> torch.Tensor:
+        # next_groups: group count of the GroupNorm that reads this block's
+        # output with nothing in between (the caller knows the successor);
+        # conv2's finalize then hands that norm its statistics, as conv1's
+        # does for norm2
         # time-emb add fused into conv1's epilogue; skip add fused into
         # conv2's. The DEEPER fusion (GN apply + SiLU inside the conv's
         # A-load, in_affine) measured SLOWER end-to-end on MI355X
@@ -422,9 +430,11 @@ class ResnetBlock(nn.Module):
             skip = self.shortcut(x) if self.shortcut is not None else x
             return self.conv2(h, residual=skip,
                               in_affine=self.norm2.coeffs(h), in_act=ops.ACT_SILU)
-        h = self.conv1(self.norm1(x), channel_bias=temb_b)
+        h = self.conv1(self.norm1(x), channel_bias=temb_b,
+                       stats_groups=self.norm2.groups)
         skip = self.shortcut(x) if self.shortcut is not None else x
-        return self.conv2(self.norm2(h), residual=skip)
+        return self.conv2(self.norm2(h), residual=skip,
+                          stats_groups=next_groups)
 
 
 def fp8_eligible_norms(unet: nn.Module) -> list:
@@ -446,8 +456,9 @@ class Downsample(nn.Module):
         super().__init__()
         self.conv = Conv2d(channels, channels, 3, stride=2)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self.conv(x)
+    def forward(self, x: torch.Tensor,
+                next_groups: int | None = None) -> torch.Tensor:
+        return self.conv(x, stats_groups=next_groups)
 
 
 class Upsample(nn.Module):
@@ -596,20 +607,38 @@ class UNet2DCondition(nn.Module):
             if self.add_embed is not None and added_cond is not None:
                 temb = temb + self.add_embed[1](ops.silu(self.add_embed[0](added_cond.to(sample.dtype))))
 
-        x = self.conv_in(sample)
+        # Each conv whose output feeds a GroupNorm with nothing in between
+        # is told that norm's group count, so its split-K finalize can hand
+        # over the statistics (ops.conv2d_nhwc stats_groups). The up path's
+        # concatenations break the chain: nothing is requested there.
+        def groups_of(norm):
+            return None if _fuse_gn() else norm.groups
+
+        x = self.conv_in(sample,
+                         stats_groups=groups_of(self.down_resnets[0].norm1))
         skips = [x]
         ri = 0
         for bi in range(len(cfg.block_out_channels)):
-            for _ in range(cfg.layers_per_block):
+            for li in range(cfg.layers_per_block):
+                if self.down_attns[ri] is not None:
+                    ng = groups_of(self.down_attns[ri].norm)
+                elif li + 1 < cfg.layers_per_block:
+                    ng = groups_of(self.down_resnets[ri + 1].norm1)
+                elif self.downsamplers[bi] is None:
+                    ng = groups_of(self.mid_res1.norm1)
+                else:
+                    ng = None  # a strided conv follows, no norm
                 x = self.down_resnets[ri](
                     x, temb,
-                    self.down_resnets[ri]._temb_b_static if use_static else None)
+                    self.down_resnets[ri]._temb_b_static if use_static else None,
+                    next_groups=ng)
                 if self.down_attns[ri] is not None:
                     x = self.down_attns[ri](x, encoder_hidden_states)
                 skips.append(x)
                 ri += 1
             if self.downsamplers[bi] is not None:
-                x = self.downsamplers[bi](x)
+                x = self.downsamplers[bi](
+                    x, next_groups=groups_of(self.down_resnets[ri].norm1))
                 skips.append(x)
 
         if control is not None:
@@ -617,7 +646,8 @@ class UNet2DCondition(nn.Module):
             skip_res, mid_res = control
             skips = [s + c for s, c in zip(skips, skip_res)]
         x = self.mid_res1(x, temb,
-                          self.mid_res1._temb_b_static if use_static else None)
+                          self.mid_res1._temb_b_static if use_static else None,
+                          next_groups=groups_of(self.mid_attn.norm))
         x = self.mid_attn(x, encoder_hidden_states)
         x = self.mid_res2(x, temb,
                           self.mid_res2._temb_b_static if use_static else None)
@@ -631,7 +661,9 @@ class UNet2DCondition(nn.Module):
                 x = torch.cat([x, skip], dim=-1)
                 x = self.up_resnets[ri](
                     x, temb,
-                    self.up_resnets[ri]._temb_b_static if use_static else None)
+                    self.up_resnets[ri]._temb_b_static if use_static else None,
+                    next_groups=(groups_of(self.up_attns[ri].norm)
+                                 if self.up_attns[ri] is not None else None))
                 if self.up_attns[ri] is not None:
                     x = self.up_attns[ri](x, encoder_hidden_states)
                 ri += 1

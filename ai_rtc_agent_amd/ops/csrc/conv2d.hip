@@ -676,6 +676,114 @@ __global__ void conv_splitk_finalize(const float* __restrict__ ws,
   }
 }
 
+// Vectorized finalize (OC % 4 == 0). A block is CT column lanes x PT pixel
+// rows (PT = 256 / CT): each lane owns 4 consecutive output channels of one
+// column tile and walks the block's pixel range, so pixel and column are
+// derived once per thread and the loop only advances pointers. Per pixel:
+// one 16 B f32 load per slab, 8 B bias/cbias/residual loads, one 8 B f16
+// store. Grid = (pixel chunks, column tiles, B). The epilogue law and order
+// are the scalar kernel's: act(sum_s slab + bias + cbias + residual).
+//
+// STATS: the column tile is a whole number of GroupNorm groups (CT*4 ==
+// gpt*Cg) and the block also emits this pixel chunk's per-group sum / sumsq
+// of the ROUNDED f16 outputs into `part` ([B*G][gridDim.x][2], the layout in
+// kernels.h) — the consumer's stats pass disappears. Fixed-order register /
+// LDS reduction, one writer per slot: deterministic, no atomics, no fence.
+typedef __attribute__((__vector_size__(4 * sizeof(_Float16)))) _Float16 f16x4;
+
+template <bool STATS>
+__global__ __launch_bounds__(256) void conv_splitk_finalize_v4(
+    const float* __restrict__ ws, const float* __restrict__ bias,
+    const f16* __restrict__ cbias, const f16* __restrict__ residual,
+    f16* __restrict__ out, float* __restrict__ part, int M, int OC,
+    int splitk, int act, int ct, int per, int Cg, int G) {
+  const int cx = threadIdx.x % ct, py = threadIdx.x / ct;
+  const int pt = 256 / ct;
+  const int cw = ct * 4;
+  const int b = blockIdx.z;
+  const int c0 = blockIdx.y * cw + cx * 4;
+  const int p_lo = blockIdx.x * per;
+  const int p_hi = min(M, p_lo + per);
+  float s4[4] = {0.f, 0.f, 0.f, 0.f}, q4[4] = {0.f, 0.f, 0.f, 0.f};
+  if (py < pt && c0 < OC) {
+    f32x4 bv = {0.f, 0.f, 0.f, 0.f}, cv = {0.f, 0.f, 0.f, 0.f};
+    if (bias) bv = *reinterpret_cast<const f32x4*>(bias + c0);
+    if (cbias) {
+      const f16x4 c = *reinterpret_cast<const f16x4*>(cbias + (long)b * OC + c0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) cv[j] = (float)c[j];
+    }
+    const long slab = (long)M * OC;
+    const long o = ((long)b * M + p_lo + py) * OC + c0;
+    const float* wp = ws + (long)b * splitk * slab + (long)(p_lo + py) * OC + c0;
+    const f16* rp = residual ? residual + o : nullptr;
+    f16* op = out + o;
+    const long step = (long)pt * OC;
+    for (int p = p_lo + py; p < p_hi; p += pt) {
+      f32x4 a = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+      for (int s = 0; s < splitk; ++s)
+        a += *reinterpret_cast<const f32x4*>(wp + (long)s * slab);
+      if (bias) a += bv;
+      if (cbias) a += cv;
+      if (rp) {
+        const f16x4 r = *reinterpret_cast<const f16x4*>(rp);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a[j] += (float)r[j];
+        rp += step;
+      }
+      f16x4 h;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        h[j] = (f16)apply_act(a[j], act);
+        if (STATS) {
+          const float f = (float)h[j];
+          s4[j] += f;
+          q4[j] += f * f;
+        }
+      }
+      *reinterpret_cast<f16x4*>(op) = h;
+      wp += step;
+      op += step;
+    }
+  }
+  if (STATS) {
+    // pt * cw <= 1024 and cw <= 128 (host plan)
+    __shared__ float red[2][1024];
+    __shared__ float col[2][128];
+    if (py < pt) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        red[0][py * cw + cx * 4 + j] = s4[j];
+        red[1][py * cw + cx * 4 + j] = q4[j];
+      }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < cw) {
+      float a0 = 0.f, a1 = 0.f;
+      for (int r = 0; r < pt; ++r) {
+        a0 += red[0][r * cw + threadIdx.x];
+        a1 += red[1][r * cw + threadIdx.x];
+      }
+      col[0][threadIdx.x] = a0;
+      col[1][threadIdx.x] = a1;
+    }
+    __syncthreads();
+    const int gpt = cw / Cg;
+    if ((int)threadIdx.x < gpt) {
+      float a0 = 0.f, a1 = 0.f;
+      for (int i = 0; i < Cg; ++i) {
+        a0 += col[0][threadIdx.x * Cg + i];
+        a1 += col[1][threadIdx.x * Cg + i];
+      }
+      const int g = blockIdx.y * gpt + threadIdx.x;
+      float* w = part + (((long)b * G + g) * gridDim.x + blockIdx.x) * 2;
+      w[0] = a0;
+      w[1] = a1;
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Small-IC conv (conv_in with IC=3/4): one thread per output PIXEL computing
 // a 64-wide OC tile in registers, weights staged once in LDS (uniform k ->
@@ -819,14 +927,81 @@ extern "C" int airtc_conv2d_splitk_for(int B, int HO, int WO, int OC, int IC) {
   return (int)(-k);
 }
 
-extern "C" void airtc_conv2d_mfma(const uint16_t* x, const uint16_t* w,
-                                  const float* bias, const uint16_t* cbias,
-                                  const uint16_t* residual, uint16_t* out,
-                                  float* ws, int B, int H, int W, int IC,
-                                  int HO, int WO, int OC, int R, int S,
-                                  int stride, int pad, int act, int path,
-                                  const float* in_aff, int in_act,
-                                  int* counters, hipStream_t s) {
+static int conv_fused_fin_env() {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("AIRTC_CONV_FUSED_FIN");
+    v = e ? atoi(e) : 0;
+  }
+  return v;
+}
+
+// A/B switch: AIRTC_FIN_VEC=0 keeps the scalar finalize (and with it no
+// fused statistics)
+static int conv_fin_vec() {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("AIRTC_FIN_VEC");
+    v = (e && atoi(e) == 0) ? 0 : 1;
+  }
+  return v;
+}
+// GroupNorm statistics from the finalize are opt-in (AIRTC_FIN_STATS=1):
+// measured NEUTRAL end-to-end on MI355X (146.9/148.2/147.1 fps with them vs
+// 147.8/147.2 without, same session, under the hipGraph): the 43 stats
+// launches they remove are paid back by the slower stats-emitting finalize
+// at 64x64 and by an apply that inherits the finalize's smaller chunk count.
+// Read per call so one process can run both.
+static int conv_fin_stats() {
+  const char* e = getenv("AIRTC_FIN_STATS");
+  return conv_fin_vec() && e && atoi(e) == 1;
+}
+
+// geometry of the vectorized finalize: ct column lanes (4 channels each),
+// per pixels per block, nchunk pixel chunks
+struct FinPlan { int ct, per, nchunk; };
+
+// stats variant: column tile = gpt whole groups (<= 128 channels, a multiple
+// of 4), nchunk <= 64 pixel chunks with no empty chunk
+static bool fin_stats_plan(int M, int OC, int G, FinPlan* p) {
+  if (G <= 0 || OC % 4 != 0 || OC % G != 0) return false;
+  const int Cg = OC / G;
+  if (Cg & 1) return false;
+  int gpt = 0;
+  for (int d = 1; d <= G; ++d)
+    if (G % d == 0 && d * Cg <= 128 && (d * Cg) % 4 == 0) gpt = d;
+  if (!gpt) return false;
+  p->ct = gpt * Cg / 4;
+  const int pt = 256 / p->ct;
+  const int n0 = min(64, ceil_div(M, pt));
+  p->per = ceil_div(M, n0);
+  p->nchunk = ceil_div(M, p->per);
+  return true;
+}
+
+extern "C" int airtc_conv2d_stats_nchunk(int B, int HO, int WO, int OC, int IC,
+                                         int G, int act) {
+  const int path = airtc_conv2d_splitk_for(B, HO, WO, OC, IC);
+  const int splitk = path > 0 ? path : -path;
+  if (path == 0 || path == 100 || splitk < 2) return 0;  // no finalize pass
+  // the env-gated experiment schedules have no separate finalize pass
+  if (act != ACT_NONE || conv_fused_fin_env() || !conv_fin_stats()) return 0;
+  if (B > 65535) return 0;  // finalize_v4 carries the batch in gridDim.z
+  const char* t = getenv("AIRTC_CONV_TILED");
+  if (t && atoi(t)) return 0;
+  FinPlan p;
+  return fin_stats_plan(HO * WO, OC, G, &p) ? p.nchunk : 0;
+}
+
+extern "C" int airtc_conv2d_mfma(const uint16_t* x, const uint16_t* w,
+                                 const float* bias, const uint16_t* cbias,
+                                 const uint16_t* residual, uint16_t* out,
+                                 float* ws, int B, int H, int W, int IC,
+                                 int HO, int WO, int OC, int R, int S,
+                                 int stride, int pad, int act, int path,
+                                 const float* in_aff, int in_act,
+                                 int* counters, float* gn_part, int gn_groups,
+                                 hipStream_t s) {
   const int K = R * S * IC;
   const f16* xp = reinterpret_cast<const f16*>(x);
   const f16* wp = reinterpret_cast<const f16*>(w);
@@ -852,7 +1027,7 @@ extern "C" void airtc_conv2d_mfma(const uint16_t* x, const uint16_t* w,
     dim3 tgrid((H >> 3) * (W >> 3), ceil_div(OC, BN), B);
     hipLaunchKernelGGL(conv3x3_tiled_kernel, tgrid, dim3(256), 0, s, xp, wp,
                        bias, cb, res, op, H, W, IC, OC, act, K);
-    return;
+    return 0;
   }
   const int splitk = path > 0 ? path : -path;
   const int bm = path > 0 ? 128 : 64;
@@ -864,12 +1039,7 @@ extern "C" void airtc_conv2d_mfma(const uint16_t* x, const uint16_t* w,
   // the per-XCD L2 reuse that feeds the K-loop — far costlier than the
   // ~105 finalize launches it removes. Env-gated for experiments
   // (AIRTC_CONV_FUSED_FIN=1); default stays the two-pass scheme.
-  static int ffin_env = -1;
-  if (ffin_env < 0) {
-    const char* e = getenv("AIRTC_CONV_FUSED_FIN");
-    ffin_env = e ? atoi(e) : 0;
-  }
-  const bool fuse_fin = ffin_env && counters != nullptr && splitk > 1;
+  const bool fuse_fin = conv_fused_fin_env() && counters != nullptr && splitk > 1;
   const float* b1 = (splitk == 1 || fuse_fin) ? bias : nullptr;
   const f16* cb1 = (splitk == 1 || fuse_fin) ? cb : nullptr;
   const f16* res1 = (splitk == 1 || fuse_fin) ? res : nullptr;
@@ -917,11 +1087,39 @@ extern "C" void airtc_conv2d_mfma(const uint16_t* x, const uint16_t* w,
 #undef CONV_LAUNCH
 #undef CONV_LAUNCH_GLDS
   if (splitk > 1 && !fuse_fin) {
-    long total = (long)B * M * OC;
-    int blocks = (int)min((long)2048, (total + 255) / 256);
-    hipLaunchKernelGGL(conv_splitk_finalize, dim3(blocks), dim3(256), 0, s, ws,
-                       bias, cb, res, op, M, OC, splitk, act, total);
+    // 16 B slab / bias loads and 8 B f16 accesses need these alignments
+    const uintptr_t al16 = (uintptr_t)ws | (uintptr_t)bias;
+    const uintptr_t al8 = (uintptr_t)cb | (uintptr_t)res | (uintptr_t)op;
+    const bool vec = conv_fin_vec() && OC % 4 == 0 && (al16 & 15) == 0 &&
+                     (al8 & 7) == 0 && B <= 65535;
+    FinPlan p;
+    if (vec && gn_part && act == ACT_NONE && fin_stats_plan(M, OC, gn_groups, &p)) {
+      dim3 fgrid(p.nchunk, OC / (p.ct * 4), B);
+      hipLaunchKernelGGL(conv_splitk_finalize_v4<true>, fgrid, dim3(256), 0, s,
+                         ws, bias, cb, res, op, gn_part, M, OC, splitk, act,
+                         p.ct, p.per, OC / gn_groups, gn_groups);
+      return 1;
+    } else if (vec) {
+      // plain geometry: up to 64 lanes across the channels, ~2048 blocks
+      const int oc4 = OC / 4;
+      const int ct = min(64, oc4);
+      const int tiles = ceil_div(oc4, ct);
+      const int pt = 256 / ct;
+      const long blocks1 = (long)ceil_div(M, pt) * tiles * B;
+      const int ppt = (int)max((long)1, min((long)8, (blocks1 + 2047) / 2048));
+      const int per = pt * ppt;
+      dim3 fgrid(ceil_div(M, per), tiles, B);
+      hipLaunchKernelGGL(conv_splitk_finalize_v4<false>, fgrid, dim3(256), 0,
+                         s, ws, bias, cb, res, op, (float*)nullptr, M, OC,
+                         splitk, act, ct, per, 0, 0);
+    } else {
+      long total = (long)B * M * OC;
+      int blocks = (int)min((long)2048, (total + 255) / 256);
+      hipLaunchKernelGGL(conv_splitk_finalize, dim3(blocks), dim3(256), 0, s,
+                         ws, bias, cb, res, op, M, OC, splitk, act, total);
+    }
   }
+  return 0;
 }
 
 extern "C" void airtc_conv2d_direct(const uint16_t* x, const uint16_t* w,

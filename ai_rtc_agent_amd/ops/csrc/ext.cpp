@@ -26,13 +26,20 @@ uint16_t* h_ptr_mut(torch::Tensor& t) {
   return reinterpret_cast<uint16_t*>(t.data_ptr<at::Half>());
 }
 
-torch::Tensor conv2d(torch::Tensor x, torch::Tensor w_perm,
-                     c10::optional<torch::Tensor> bias,
-                     c10::optional<torch::Tensor> cbias,
-                     c10::optional<torch::Tensor> residual, int64_t R,
-                     int64_t S, int64_t stride, int64_t pad, int64_t act,
-                     c10::optional<torch::Tensor> in_affine, int64_t in_act,
-                     c10::optional<torch::Tensor> counters) {
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// stats_groups > 0 asks the split-K finalize for GroupNorm partials of the
+// output (kernels.h layout); *gn_part stays undefined when the shape takes
+// no finalize pass or the finalize cannot produce them
+torch::Tensor conv2d_impl(torch::Tensor x, torch::Tensor w_perm,
+                          c10::optional<torch::Tensor> bias,
+                          c10::optional<torch::Tensor> cbias,
+                          c10::optional<torch::Tensor> residual, int64_t R,
+                          int64_t S, int64_t stride, int64_t pad, int64_t act,
+                          c10::optional<torch::Tensor> in_affine,
+                          int64_t in_act,
+                          c10::optional<torch::Tensor> counters,
+                          int64_t stats_groups, torch::Tensor* gn_part) {
   CHECK_IN(x);
   CHECK_IN(w_perm);
   TORCH_CHECK(x.dtype() == torch::kHalf && w_perm.dtype() == torch::kHalf);
@@ -91,11 +98,55 @@ torch::Tensor conv2d(torch::Tensor x, torch::Tensor w_perm,
                 "counters buffer too small");
     cnt = counters->data_ptr<int>();
   }
-  airtc_conv2d_mfma(h_ptr(x), h_ptr(w_perm), bp, cb, res, h_ptr_mut(out), wsp,
-                    B, H, W, IC, HO, WO, OC, (int)R, (int)S, (int)stride,
-                    (int)pad, (int)act, path, aff, (int)in_act, cnt,
-                    cur_stream());
+  float* gnp = nullptr;
+  if (gn_part && stats_groups > 0 && aligned16(bp) && aligned16(cb) &&
+      aligned16(res)) {
+    const int npart = airtc_conv2d_stats_nchunk(B, HO, WO, OC, IC,
+                                                (int)stats_groups, (int)act);
+    if (npart > 0) {
+      *gn_part = torch::empty({(long)B * stats_groups, npart, 2},
+                              x.options().dtype(torch::kFloat));
+      gnp = gn_part->data_ptr<float>();
+    }
+  }
+  const int wrote = airtc_conv2d_mfma(
+      h_ptr(x), h_ptr(w_perm), bp, cb, res, h_ptr_mut(out), wsp, B, H, W, IC,
+      HO, WO, OC, (int)R, (int)S, (int)stride, (int)pad, (int)act, path, aff,
+      (int)in_act, cnt, gnp, (int)stats_groups, cur_stream());
+  // the launcher has the last word: partials it did not write are dropped,
+  // and the consumer norm runs its own statistics pass
+  if (gnp && !wrote) *gn_part = torch::Tensor();
   return out;
+}
+
+torch::Tensor conv2d(torch::Tensor x, torch::Tensor w_perm,
+                     c10::optional<torch::Tensor> bias,
+                     c10::optional<torch::Tensor> cbias,
+                     c10::optional<torch::Tensor> residual, int64_t R,
+                     int64_t S, int64_t stride, int64_t pad, int64_t act,
+                     c10::optional<torch::Tensor> in_affine, int64_t in_act,
+                     c10::optional<torch::Tensor> counters) {
+  return conv2d_impl(x, w_perm, bias, cbias, residual, R, S, stride, pad, act,
+                     in_affine, in_act, counters, 0, nullptr);
+}
+
+// conv2d + GroupNorm partials for the consumer norm: (out, partials | None)
+pybind11::tuple conv2d_stats(torch::Tensor x, torch::Tensor w_perm,
+                             c10::optional<torch::Tensor> bias,
+                             c10::optional<torch::Tensor> cbias,
+                             c10::optional<torch::Tensor> residual, int64_t R,
+                             int64_t S, int64_t stride, int64_t pad,
+                             int64_t act,
+                             c10::optional<torch::Tensor> in_affine,
+                             int64_t in_act,
+                             c10::optional<torch::Tensor> counters,
+                             int64_t stats_groups) {
+  torch::Tensor part;
+  auto out = conv2d_impl(x, w_perm, bias, cbias, residual, R, S, stride, pad,
+                         act, in_affine, in_act, counters, stats_groups,
+                         &part);
+  if (part.defined()) return pybind11::make_tuple(out, part);
+  return pybind11::make_tuple(out, pybind11::none());
 }
 
 torch::Tensor group_norm_coeffs(torch::Tensor x, int64_t groups,
@@ -106,8 +157,7 @@ torch::Tensor group_norm_coeffs(torch::Tensor x, int64_t groups,
   const int C = x.size(-1);
   const long HW = x.numel() / ((long)B * C);
   auto coeffs = torch::empty({B, C, 2}, x.options().dtype(torch::kFloat));
-  const int nchunk = airtc_group_norm_nchunk(B, (int)groups);
-  auto ws = torch::empty({(long)B * groups * nchunk * 2},
+  auto ws = torch::empty({(long)B * groups * AIRTC_GN_MAX_PART * 2},
                          x.options().dtype(torch::kFloat));
   airtc_group_norm_coeffs(h_ptr(x), gamma.data_ptr<float>(),
                           beta.data_ptr<float>(), coeffs.data_ptr<float>(),
@@ -116,17 +166,37 @@ torch::Tensor group_norm_coeffs(torch::Tensor x, int64_t groups,
   return coeffs;
 }
 
+// partials handed over by a producer (conv2d_stats): validated here, the
+// launcher trusts the count
+int check_partials(const torch::Tensor& p, int B, int64_t groups) {
+  CHECK_IN(p);
+  TORCH_CHECK(p.dtype() == torch::kFloat && p.dim() == 3 &&
+                  p.size(0) == (long)B * groups && p.size(2) == 2 &&
+                  p.size(1) >= 1 && p.size(1) <= AIRTC_GN_MAX_PART,
+              "partials must be f32 (B*G, npart <= 64, 2)");
+  return (int)p.size(1);
+}
+
 torch::Tensor group_norm_silu_fp8(torch::Tensor x, int64_t groups,
                                   torch::Tensor gamma, torch::Tensor beta,
-                                  double eps, int64_t act, double a_scale) {
+                                  double eps, int64_t act, double a_scale,
+                                  c10::optional<torch::Tensor> partials) {
   CHECK_IN(x);
   TORCH_CHECK(x.dtype() == torch::kHalf);
   const int B = x.size(0);
   const int C = x.size(-1);
   const long HW = x.numel() / ((long)B * C);
   auto out = torch::empty_like(x, x.options().dtype(torch::kUInt8));
-  const int nchunk = airtc_group_norm_nchunk(B, (int)groups);
-  auto ws = torch::empty({(long)B * groups * nchunk * 2},
+  if (partials.has_value()) {
+    const int npart = check_partials(*partials, B, groups);
+    airtc_group_norm_apply(h_ptr(x), partials->data_ptr<float>(), npart,
+                           gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                           nullptr, out.data_ptr<uint8_t>(), B, (int)HW, C,
+                           (int)groups, (float)eps, (int)act, (float)a_scale,
+                           cur_stream());
+    return out;
+  }
+  auto ws = torch::empty({(long)B * groups * AIRTC_GN_MAX_PART * 2},
                          x.options().dtype(torch::kFloat));
   airtc_group_norm_silu_fp8(h_ptr(x), gamma.data_ptr<float>(),
                             beta.data_ptr<float>(), out.data_ptr<uint8_t>(),
@@ -138,14 +208,22 @@ torch::Tensor group_norm_silu_fp8(torch::Tensor x, int64_t groups,
 
 torch::Tensor group_norm_silu(torch::Tensor x, int64_t groups,
                               torch::Tensor gamma, torch::Tensor beta,
-                              double eps, int64_t act) {
+                              double eps, int64_t act,
+                              c10::optional<torch::Tensor> partials) {
   CHECK_IN(x);
   const int B = x.size(0);
   const int C = x.size(-1);
   const long HW = x.numel() / ((long)B * C);
   auto out = torch::empty_like(x);
-  const int nchunk = airtc_group_norm_nchunk(B, (int)groups);
-  auto ws = torch::empty({(long)B * groups * nchunk * 2},
+  if (partials.has_value()) {
+    const int npart = check_partials(*partials, B, groups);
+    airtc_group_norm_apply(h_ptr(x), partials->data_ptr<float>(), npart,
+                           gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                           h_ptr_mut(out), nullptr, B, (int)HW, C, (int)groups,
+                           (float)eps, (int)act, 1.0f, cur_stream());
+    return out;
+  }
+  auto ws = torch::empty({(long)B * groups * AIRTC_GN_MAX_PART * 2},
                          x.options().dtype(torch::kFloat));
   airtc_group_norm_silu(h_ptr(x), gamma.data_ptr<float>(),
                         beta.data_ptr<float>(), h_ptr_mut(out),
@@ -588,9 +666,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("act"), pybind11::arg("in_affine") = pybind11::none(),
         pybind11::arg("in_act") = 0,
         pybind11::arg("counters") = pybind11::none());
-  m.def("group_norm_silu", &group_norm_silu);
+  m.def("conv2d_stats", &conv2d_stats,
+        "conv2d that also returns GroupNorm partials of its output for a "
+        "consumer norm with stats_groups groups: (out, partials | None)",
+        pybind11::arg("x"), pybind11::arg("w_perm"), pybind11::arg("bias"),
+        pybind11::arg("cbias"), pybind11::arg("residual"), pybind11::arg("R"),
+        pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"),
+        pybind11::arg("act"), pybind11::arg("in_affine"),
+        pybind11::arg("in_act"), pybind11::arg("counters"),
+        pybind11::arg("stats_groups"));
+  m.def("group_norm_silu", &group_norm_silu, pybind11::arg("x"),
+        pybind11::arg("groups"), pybind11::arg("gamma"), pybind11::arg("beta"),
+        pybind11::arg("eps"), pybind11::arg("act"),
+        pybind11::arg("partials") = pybind11::none());
   m.def("group_norm_silu_fp8", &group_norm_silu_fp8,
-        "GN+act writing e4m3 codes (producer-side fp8 quantization)");
+        "GN+act writing e4m3 codes (producer-side fp8 quantization)",
+        pybind11::arg("x"), pybind11::arg("groups"), pybind11::arg("gamma"),
+        pybind11::arg("beta"), pybind11::arg("eps"), pybind11::arg("act"),
+        pybind11::arg("a_scale"),
+        pybind11::arg("partials") = pybind11::none());
   m.def("group_norm_coeffs", &group_norm_coeffs,
         "(B,C,2) f32 affine pairs for the fused GN->conv input transform");
   m.def("layer_norm", &layer_norm);

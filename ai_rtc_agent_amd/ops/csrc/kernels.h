@@ -36,7 +36,22 @@ void airtc_sched_blend(const uint16_t* xt, const uint16_t* eps,
                        hipStream_t s);
 
 // norms ---------------------------------------------------------------------
+// GroupNorm partial statistics, the one layout every producer and consumer
+// shares: f32 [B*G][npart][2] = per (batch, group), npart partial
+// (sum, sumsq) pairs over disjoint parts of the group's HW*Cg elements;
+// consumers add the npart pairs in index order. npart is chosen by the
+// producer and is <= AIRTC_GN_MAX_PART, so a ws of
+// B*G*AIRTC_GN_MAX_PART*2 floats always fits.
+#define AIRTC_GN_MAX_PART 64
 int airtc_group_norm_nchunk(int B, int G);
+// apply only, on partials from another producer (the split-K finalize with
+// gn_part below); exactly one of out / out_q8 is non-null
+void airtc_group_norm_apply(const uint16_t* x, const float* part, int npart,
+                            const float* gamma, const float* beta,
+                            uint16_t* out, uint8_t* out_q8, int B, int HW,
+                            int C, int G, float eps, int act, float a_scale,
+                            hipStream_t s);
+// ws for the three launchers below: B*G*AIRTC_GN_MAX_PART*2 floats
 void airtc_group_norm_silu(const uint16_t* x, const float* gamma,
                            const float* beta, uint16_t* out, float* ws, int B,
                            int HW, int C, int G, float eps, int act,
@@ -67,12 +82,23 @@ void airtc_group_norm_coeffs(const uint16_t* x, const float* gamma,
 int airtc_conv2d_splitk_for(int B, int HO, int WO, int OC, int IC);
 // in_aff: optional (B, IC, 2) f32 per-channel input affine (fused GN) with
 // in_act applied after — transforms x AT LOAD TIME (padding stays zero)
-void airtc_conv2d_mfma(const uint16_t* x, const uint16_t* w, const float* bias,
-                       const uint16_t* cbias, const uint16_t* residual,
-                       uint16_t* out, float* ws, int B, int H, int W, int IC,
-                       int HO, int WO, int OC, int R, int S, int stride,
-                       int pad, int act, int path, const float* in_aff,
-                       int in_act, int* counters, hipStream_t s);
+// Returns 1 when gn_part was written, 0 otherwise (the caller must then drop
+// the buffer: nothing initialised it).
+int airtc_conv2d_mfma(const uint16_t* x, const uint16_t* w, const float* bias,
+                      const uint16_t* cbias, const uint16_t* residual,
+                      uint16_t* out, float* ws, int B, int H, int W, int IC,
+                      int HO, int WO, int OC, int R, int S, int stride,
+                      int pad, int act, int path, const float* in_aff,
+                      int in_act, int* counters, float* gn_part,
+                      int gn_groups, hipStream_t s);
+// gn_part: optional GroupNorm partials of the OUTPUT for a consumer norm
+// with gn_groups groups (layout above), written by the split-K finalize from
+// the rounded f16 values. Pass it only when airtc_conv2d_stats_nchunk
+// returns npart > 0 (split-K path, act == ACT_NONE, OC % 4 == 0, even
+// OC/G, B <= 65535); size B*G*npart*2 floats; bias / cbias / residual 16 B
+// aligned.
+int airtc_conv2d_stats_nchunk(int B, int HO, int WO, int OC, int IC, int G,
+                              int act);
 void airtc_conv2d_direct(const uint16_t* x, const uint16_t* w,
                          const float* bias, const uint16_t* cbias,
                          const uint16_t* residual, uint16_t* out, int B, int H,

@@ -7,6 +7,8 @@
 //
 // layer_norm: one wave per row (transformer blocks), f16x8 loads, f32 stats.
 
+#include <stdlib.h>
+
 #include "common.h"
 
 // ---------------------------------------------------------------------------
@@ -163,6 +165,214 @@ extern "C" int airtc_group_norm_nchunk(int B, int G) {
   return n;
 }
 
+// ---------------------------------------------------------------------------
+// C % 8 == 0 fast path: 16 B accesses, no per-element integer division.
+//
+// A block is CT column lanes x PT pixel rows (PT = 256 / CT). Each lane owns
+// 8 consecutive channels of the block's column tile and walks the block's
+// pixel range, so the loop only advances a pointer. A 16 B vector may
+// straddle group boundaries (Cg = 10, 30): statistics are therefore kept
+// per CHANNEL in registers and folded to groups through LDS, and the apply
+// pass reads per-channel (s, t) = (gamma*rstd, beta - mean*s) from an LDS
+// table built in the prologue — one FMA plus the activation per element.
+// The column tile is a whole number of groups (CT*8 == gpt*Cg), so every
+// group's partial has exactly one writer: fixed-order, deterministic.
+// Grid = (pixel chunks, column tiles, B).
+// ---------------------------------------------------------------------------
+struct GnPlan { int gpt, ct, pt; };
+
+static bool gn_fast_plan(int C, int G, GnPlan* p) {
+  if (G <= 0 || C % 8 != 0 || C % G != 0) return false;
+  const int Cg = C / G;
+  int gpt = 0;
+  for (int d = 1; d <= G && d <= 64; ++d)
+    if (G % d == 0 && (d * Cg) % 8 == 0 && d * Cg <= 512) gpt = d;
+  if (!gpt) return false;
+  p->gpt = gpt;
+  p->ct = gpt * Cg / 8;
+  p->pt = 256 / p->ct;
+  return true;
+}
+
+__global__ __launch_bounds__(256) void group_norm_stats_v8_kernel(
+    const f16* __restrict__ x, float* __restrict__ part, int HW, int C, int G,
+    int ct, int per) {
+  // pt * cw <= 2048 and cw <= 512 (gn_fast_plan)
+  __shared__ float red[2][2048];
+  __shared__ float col[2][512];
+  const int cx = threadIdx.x % ct, py = threadIdx.x / ct;
+  const int pt = 256 / ct;
+  const int cw = ct * 8;
+  const int b = blockIdx.z;
+  const int p_lo = blockIdx.x * per;
+  const int p_hi = min(HW, p_lo + per);
+  if (py < pt) {
+    float s[8], q[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.f;
+    const f16* xp = x + ((long)b * HW + p_lo + py) * C + blockIdx.y * cw + cx * 8;
+    const long step = (long)pt * C;
+#pragma unroll 2
+    for (int p = p_lo + py; p < p_hi; p += pt, xp += step) {
+      const f16x8 v = *reinterpret_cast<const f16x8*>(xp);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float f = (float)v[j];
+        s[j] += f;
+        q[j] += f * f;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      red[0][py * cw + cx * 8 + j] = s[j];
+      red[1][py * cw + cx * 8 + j] = q[j];
+    }
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < cw; c += 256) {
+    float a0 = 0.f, a1 = 0.f;
+    for (int r = 0; r < pt; ++r) {
+      a0 += red[0][r * cw + c];
+      a1 += red[1][r * cw + c];
+    }
+    col[0][c] = a0;
+    col[1][c] = a1;
+  }
+  __syncthreads();
+  const int Cg = C / G;
+  const int gpt = cw / Cg;
+  if ((int)threadIdx.x < gpt) {
+    float a0 = 0.f, a1 = 0.f;
+    for (int i = 0; i < Cg; ++i) {
+      a0 += col[0][threadIdx.x * Cg + i];
+      a1 += col[1][threadIdx.x * Cg + i];
+    }
+    const int g = blockIdx.y * gpt + threadIdx.x;
+    float* w = part + (((long)b * G + g) * gridDim.x + blockIdx.x) * 2;
+    w[0] = a0;
+    w[1] = a1;
+  }
+}
+
+// Q8: write e4m3 codes (see group_norm_apply_fp8_kernel) instead of f16
+template <bool Q8>
+__global__ __launch_bounds__(256) void group_norm_apply_v8_kernel(
+    const f16* __restrict__ x, const float* __restrict__ part,
+    const float* __restrict__ gamma, const float* __restrict__ beta,
+    f16* __restrict__ out, uint8_t* __restrict__ outq, int HW, int C, int G,
+    int npart, float eps, int act, float inv_sa, int ct, int per) {
+  __shared__ float gst[2][64];
+  __shared__ float tab[2][512];
+  const int cx = threadIdx.x % ct, py = threadIdx.x / ct;
+  const int pt = 256 / ct;
+  const int cw = ct * 8;
+  const int b = blockIdx.z;
+  const int ch0 = blockIdx.y * cw;
+  const int Cg = C / G;
+  const int gpt = cw / Cg;
+  // fold the tiny cross-chunk reduction into every block (npart <= 64)
+  if ((int)threadIdx.x < gpt) {
+    const int g = blockIdx.y * gpt + threadIdx.x;
+    const float* w = &part[((long)b * G + g) * npart * 2];
+    float s0 = 0.f, s1 = 0.f;
+    for (int i = 0; i < npart; ++i) { s0 += w[2 * i]; s1 += w[2 * i + 1]; }
+    const float n = (float)HW * Cg;
+    const float mean = s0 / n;
+    gst[0][threadIdx.x] = mean;
+    gst[1][threadIdx.x] = rsqrtf(s1 / n - mean * mean + eps);
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < cw; c += 256) {
+    const int gi = c / Cg;
+    const float sc = gamma[ch0 + c] * gst[1][gi];
+    tab[0][c] = sc;
+    tab[1][c] = beta[ch0 + c] - gst[0][gi] * sc;
+  }
+  __syncthreads();
+  if (py >= pt) return;
+  float sc[8], sh[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    sc[j] = tab[0][cx * 8 + j];
+    sh[j] = tab[1][cx * 8 + j];
+  }
+  const int p_lo = blockIdx.x * per;
+  const int p_hi = min(HW, p_lo + per);
+  long idx = ((long)b * HW + p_lo + py) * C + ch0 + cx * 8;
+  const long step = (long)pt * C;
+#pragma unroll 2
+  for (int p = p_lo + py; p < p_hi; p += pt, idx += step) {
+    f16x8 v = *reinterpret_cast<const f16x8*>(&x[idx]);
+    if (Q8) {
+      float a[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float t = (float)v[j] * sc[j] + sh[j];
+        a[j] = fminf(fmaxf(apply_act(t, act) * inv_sa, -448.0f), 448.0f);
+      }
+      int w0 = __builtin_amdgcn_cvt_pk_fp8_f32(a[0], a[1], 0, false);
+      w0 = __builtin_amdgcn_cvt_pk_fp8_f32(a[2], a[3], w0, true);
+      int w1 = __builtin_amdgcn_cvt_pk_fp8_f32(a[4], a[5], 0, false);
+      w1 = __builtin_amdgcn_cvt_pk_fp8_f32(a[6], a[7], w1, true);
+      uint2 q;
+      q.x = (uint32_t)w0;
+      q.y = (uint32_t)w1;
+      *reinterpret_cast<uint2*>(&outq[idx]) = q;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        v[j] = (f16)apply_act((float)v[j] * sc[j] + sh[j], act);
+      *reinterpret_cast<f16x8*>(&out[idx]) = v;
+    }
+  }
+}
+
+// stats launch of the fast path; returns the partial count it wrote
+static int gn_launch_stats_v8(const GnPlan& pl, const f16* x, float* part,
+                              int B, int HW, int C, int G, hipStream_t s) {
+  const int n0 = min(64, ceil_div(HW, pl.pt));
+  const int per = ceil_div(HW, n0);
+  const int npart = ceil_div(HW, per);  // <= 64, no empty chunk
+  hipLaunchKernelGGL(group_norm_stats_v8_kernel, dim3(npart, G / pl.gpt, B),
+                     dim3(256), 0, s, x, part, HW, C, G, pl.ct, per);
+  return npart;
+}
+
+static void gn_launch_apply_v8(const GnPlan& pl, const f16* x,
+                               const float* part, int npart,
+                               const float* gamma, const float* beta, f16* out,
+                               uint8_t* outq, int B, int HW, int C, int G,
+                               float eps, int act, float inv_sa,
+                               hipStream_t s) {
+  // ~512 blocks, at least one pixel per thread row
+  const int tiles = G / pl.gpt;
+  int nch = ceil_div(512, tiles * B);
+  nch = max(1, min(nch, ceil_div(HW, pl.pt)));
+  const int per = ceil_div(HW, nch);
+  dim3 grid(ceil_div(HW, per), tiles, B);
+  if (outq)
+    hipLaunchKernelGGL(group_norm_apply_v8_kernel<true>, grid, dim3(256), 0, s,
+                       x, part, gamma, beta, out, outq, HW, C, G, npart, eps,
+                       act, inv_sa, pl.ct, per);
+  else
+    hipLaunchKernelGGL(group_norm_apply_v8_kernel<false>, grid, dim3(256), 0,
+                       s, x, part, gamma, beta, out, outq, HW, C, G, npart,
+                       eps, act, inv_sa, pl.ct, per);
+}
+
+static bool gn_fast_ok(const void* x, const void* out, int B, int C, int G,
+                       GnPlan* pl) {
+  // Opt-in (AIRTC_GN_FAST=1): measured SLOWER end-to-end on MI355X at SD
+  // shapes (144.5/144.6 fps with it vs 145.7/146.8 without, same session;
+  // 64x64x320 stats+apply 14.7 us vs 12.1 us): at B=1 the <= 64 pixel chunks per
+  // column tile leave the stats pass on ~64 blocks of serial loads, where
+  // the f16x2 kernels spread 512. Read per call so one process can run both.
+  const char* e = getenv("AIRTC_GN_FAST");
+  if (!(e && atoi(e) == 1) || B > 65535) return false;
+  if ((((uintptr_t)x | (uintptr_t)out) & 15) != 0) return false;
+  return gn_fast_plan(C, G, pl);
+}
+
 // per-(b, channel) affine pairs for the fused GN->conv input transform
 // (conv2d.hip load_a): s = gamma_c * rstd_g, t = beta_c - mean_g * s.
 // Replaces the full-tensor apply pass when the ONLY consumer is a conv.
@@ -215,13 +425,52 @@ extern "C" void airtc_group_norm_silu(const uint16_t* x, const float* gamma,
                                       const float* beta, uint16_t* out,
                                       float* ws, int B, int HW, int C, int G,
                                       float eps, int act, hipStream_t s) {
+  const f16* xp = reinterpret_cast<const f16*>(x);
+  GnPlan pl;
+  if (gn_fast_ok(x, out, B, C, G, &pl)) {
+    const int npart = gn_launch_stats_v8(pl, xp, ws, B, HW, C, G, s);
+    gn_launch_apply_v8(pl, xp, ws, npart, gamma, beta,
+                       reinterpret_cast<f16*>(out), nullptr, B, HW, C, G, eps,
+                       act, 0.f, s);
+    return;
+  }
   const int nchunk = airtc_group_norm_nchunk(B, G);
   dim3 grid(B * G, nchunk);
-  hipLaunchKernelGGL(group_norm_stats_kernel, grid, dim3(256), 0, s,
-                     reinterpret_cast<const f16*>(x), ws, HW, C, G, nchunk);
-  hipLaunchKernelGGL(group_norm_apply_kernel, grid, dim3(256), 0, s,
-                     reinterpret_cast<const f16*>(x), ws, gamma, beta,
-                     reinterpret_cast<f16*>(out), HW, C, G, nchunk, eps, act);
+  hipLaunchKernelGGL(group_norm_stats_kernel, grid, dim3(256), 0, s, xp, ws,
+                     HW, C, G, nchunk);
+  hipLaunchKernelGGL(group_norm_apply_kernel, grid, dim3(256), 0, s, xp, ws,
+                     gamma, beta, reinterpret_cast<f16*>(out), HW, C, G,
+                     nchunk, eps, act);
+}
+
+// Apply only, on partial statistics somebody else produced (the split-K
+// finalize, conv2d.hip): part is [B*G][npart][2], npart <= 64. Exactly one
+// of out / out_q8 is non-null (f16 result, or e4m3 codes at a_scale).
+extern "C" void airtc_group_norm_apply(const uint16_t* x, const float* part,
+                                       int npart, const float* gamma,
+                                       const float* beta, uint16_t* out,
+                                       uint8_t* out_q8, int B, int HW, int C,
+                                       int G, float eps, int act,
+                                       float a_scale, hipStream_t s) {
+  const f16* xp = reinterpret_cast<const f16*>(x);
+  f16* op = reinterpret_cast<f16*>(out);
+  const float inv_sa = out_q8 ? 1.0f / a_scale : 0.f;
+  GnPlan pl;
+  if (gn_fast_ok(x, out_q8 ? (const void*)out_q8 : (const void*)out, B, C, G,
+                 &pl)) {
+    gn_launch_apply_v8(pl, xp, part, npart, gamma, beta, op, out_q8, B, HW, C,
+                       G, eps, act, inv_sa, s);
+    return;
+  }
+  // the f16x2 kernels chunk their own work by the partial count
+  dim3 grid(B * G, npart);
+  if (out_q8)
+    hipLaunchKernelGGL(group_norm_apply_fp8_kernel, grid, dim3(256), 0, s, xp,
+                       part, gamma, beta, out_q8, HW, C, G, npart, eps, act,
+                       inv_sa);
+  else
+    hipLaunchKernelGGL(group_norm_apply_kernel, grid, dim3(256), 0, s, xp,
+                       part, gamma, beta, op, HW, C, G, npart, eps, act);
 }
 
 extern "C" void airtc_group_norm_silu_fp8(const uint16_t* x,
@@ -230,6 +479,14 @@ extern "C" void airtc_group_norm_silu_fp8(const uint16_t* x,
                                           float* ws, int B, int HW, int C,
                                           int G, float eps, int act,
                                           float a_scale, hipStream_t s) {
+  GnPlan pl;
+  if (gn_fast_ok(x, out, B, C, G, &pl)) {
+    const f16* xp = reinterpret_cast<const f16*>(x);
+    const int npart = gn_launch_stats_v8(pl, xp, ws, B, HW, C, G, s);
+    gn_launch_apply_v8(pl, xp, ws, npart, gamma, beta, nullptr, out, B, HW, C,
+                       G, eps, act, 1.0f / a_scale, s);
+    return;
+  }
   const int nchunk = airtc_group_norm_nchunk(B, G);
   dim3 grid(B * G, nchunk);
   hipLaunchKernelGGL(group_norm_stats_kernel, grid, dim3(256), 0, s,

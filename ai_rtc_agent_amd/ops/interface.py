@@ -92,6 +92,7 @@ def conv2d_nhwc(
     channel_bias: torch.Tensor | None = None,
     in_affine: torch.Tensor | None = None,
     in_act: int = ACT_NONE,
+    stats_groups: int | None = None,
 ) -> torch.Tensor:
     """x: (B,H,W,C) contiguous; weight: (O,I,R,S) [torch layout]; out (B,H',W',O).
 
@@ -107,6 +108,14 @@ def conv2d_nhwc(
       every input element AT LOAD TIME — the fused-GroupNorm path
       (group_norm_coeffs); the producing apply kernel and its activation
       round-trip through HBM disappear.
+    stats_groups: the group count G of a GroupNorm that consumes THIS
+      output directly. On split-K shapes the finalize pass then also emits
+      the norm's partial sum/sumsq, and they ride on the returned tensor as
+      `_airtc_gn_part` for group_norm_silu_nhwc, whose own stats pass
+      disappears. Only a hint, and opt-in (AIRTC_FIN_STATS=1; measured
+      neutral end to end): without the switch, on shapes that take no
+      finalize pass and on the CPU reference path nothing is attached and
+      the norm runs as usual.
     """
     if act is None:
         act = ACT_SILU if fuse_silu else ACT_NONE
@@ -131,7 +140,8 @@ def conv2d_nhwc(
             )
             return conv2d_nhwc(xp, w_pad, bias, stride, padding, fuse_silu,
                                act=act, residual=residual,
-                               channel_bias=channel_bias)
+                               channel_bias=channel_bias,
+                               stats_groups=stats_groups)
         w_perm = _cached(
             weight,
             "_airtc_wperm",
@@ -153,7 +163,7 @@ def conv2d_nhwc(
                 weight._airtc_skcnt = cnt
             except AttributeError:
                 pass
-        return ext.conv2d(
+        args = (
             x,
             w_perm,
             b32,
@@ -168,6 +178,14 @@ def conv2d_nhwc(
             in_act,
             cnt,
         )
+        if stats_groups and act == ACT_NONE:
+            y, part = ext.conv2d_stats(*args, stats_groups)
+            if part is not None:
+                # (partials, G, version): the norm ignores them if the
+                # tensor was written in place after the conv
+                y._airtc_gn_part = (part, stats_groups, y._version)
+            return y
+        return ext.conv2d(*args)
 
     if in_affine is not None:
         aff = in_affine.float()
@@ -385,10 +403,16 @@ def group_norm_silu_nhwc(
         g32 = _cached(gamma, "_airtc_g32", lambda: gamma.detach().float().contiguous())
         b32 = _cached(beta, "_airtc_b32", lambda: beta.detach().float().contiguous())
         act = ACT_SILU if silu else ACT_NONE
+        # partial statistics the producing conv's finalize left on x
+        # (conv2d_nhwc stats_groups): same tensor, same G, unmodified since
+        part = None
+        tag = getattr(x, "_airtc_gn_part", None)
+        if tag is not None and tag[1] == num_groups and tag[2] == x._version:
+            part = tag[0]
         if fp8_scale is not None:
             return ext.group_norm_silu_fp8(x, num_groups, g32, b32, eps, act,
-                                           fp8_scale)
-        return ext.group_norm_silu(x, num_groups, g32, b32, eps, act)
+                                           fp8_scale, part)
+        return ext.group_norm_silu(x, num_groups, g32, b32, eps, act, part)
     b, h, w, c = x.shape
     xc = x.permute(0, 3, 1, 2).float()
     y = F.group_norm(xc, num_groups, gamma.float(), beta.float(), eps)

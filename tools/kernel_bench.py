@@ -128,6 +128,45 @@ def main():
     us = timeit(lambda: ops.group_norm_silu_nhwc(x, 32, g, be), args.iters)
     traffic = x.numel() * 2 * 3  # 2 reads (stats+apply) + 1 write
     print(f"  {'group_norm_silu 64x64x320':32s} {us:8.1f} us  {traffic/us/1e3:7.1f} GB/s")
+
+    # the conv -> GroupNorm chain with and without the statistics fused into
+    # the split-K finalize. The finalize has no entry point of its own: its
+    # cost is the difference of the two conv rows (plain vs stats), and its
+    # absolute time is in the kernel-trace profiles
+    # (profiles/kernel_time_rounds.md). The statistics are opt-in and read
+    # per call; only the calls that pass stats_groups see the switch.
+    os.environ["AIRTC_FIN_STATS"] = "1"
+    print("== conv -> GroupNorm chain (fused = finalize emits the statistics) ==")
+    for h, c in ((64, 320), (32, 640), (16, 1280)):
+        xc = torch.randn(1, h, h, c, device=dev).half()
+        wt = (torch.randn(c, c, 3, 3, device=dev) * 0.02).half()
+        cb = torch.randn(1, c, device=dev).half()
+        gc = torch.randn(c, device=dev).float()
+        bc = torch.randn(c, device=dev).float()
+        y_plain = ops.conv2d_nhwc(xc, wt, None, channel_bias=cb)
+        y_stats = ops.conv2d_nhwc(xc, wt, None, channel_bias=cb, stats_groups=32)
+        fused_ok = hasattr(y_stats, "_airtc_gn_part")
+        rows = [
+            ("conv+finalize", lambda: ops.conv2d_nhwc(xc, wt, None, channel_bias=cb)),
+            ("conv+finalize(stats)", lambda: ops.conv2d_nhwc(
+                xc, wt, None, channel_bias=cb, stats_groups=32)),
+            ("gn stats+apply", lambda: ops.group_norm_silu_nhwc(y_plain, 32, gc, bc)),
+            ("gn apply only", lambda: ops.group_norm_silu_nhwc(y_stats, 32, gc, bc)),
+            ("chain unfused", lambda: ops.group_norm_silu_nhwc(
+                ops.conv2d_nhwc(xc, wt, None, channel_bias=cb), 32, gc, bc)),
+            ("chain fused", lambda: ops.group_norm_silu_nhwc(
+                ops.conv2d_nhwc(xc, wt, None, channel_bias=cb, stats_groups=32),
+                32, gc, bc)),
+        ]
+        # interleaved repeats: every row is timed in each of 3 rounds
+        best = {n: float("inf") for n, _ in rows}
+        for _ in range(3):
+            for n, fn in rows:
+                best[n] = min(best[n], timeit(fn, args.iters))
+        if not fused_ok:
+            print(f"  ({h}x{h}x{c}: the conv attached no partials)")
+        for n, _ in rows:
+            print(f"  {n + f' {h}x{h}x{c}':36s} {best[n]:8.1f} us")
     t = torch.randn(1, 4096, 320, device=dev).half()
     us = timeit(lambda: ops.layer_norm(t, g, be), args.iters)
     print(f"  {'layer_norm 4096x320':32s} {us:8.1f} us  {t.numel()*2*2/us/1e3:7.1f} GB/s")
