@@ -70,12 +70,15 @@ __device__ __forceinline__ f16x8 tr_bfrag(const f16* tile, int pitch,
   return cvt.f8;
 }
 
-template <int D, int QF, int KT = KVT>  // QF = q-frags/wave; KT = kv tile
+template <int D, int KT = KVT>  // KT = kv tile
 __global__ __launch_bounds__(256) void attention_kernel(
     const f16* __restrict__ q, const f16* __restrict__ k,
     const f16* __restrict__ v, f16* __restrict__ out, int H, int Lq, int Lk,
     long q_sb, long q_sh, long q_row, long k_sb, long k_sh, long k_row,
-    long o_sb, long o_sh, long o_row, float scale, int n_qt, int xcd_map) {
+    long o_sb, long o_sh, long o_row, float scale) {
+  // q-fragments per wave. 2 (128-row q-tiles) measured slower end to end
+  // (profiles/optimization_ladder.md, "Retired experiments").
+  constexpr int QF = 1;
   constexpr int KPITCH = D + 8;
   constexpr int D8 = D / 8, D32 = D / 32, D16 = D / 16;
   constexpr int NF = KT / 16;     // 16-key S fragments per tile
@@ -89,23 +92,8 @@ __global__ __launch_bounds__(256) void attention_kernel(
   __shared__ f16 ldsV[KT * KPITCH];  // row-major like K; PV reads via tr_b16
   __shared__ f16 ldsP[4 * KT * PT_PITCH];
 
-  // XCD-chunked mapping (env AIRTC_ATTN_XCD): each XCD walks a CONTIGUOUS
-  // (head, q-tile) range, so one XCD's in-flight blocks share 1-2 heads'
-  // K/V (~1-2 MB) and re-reads hit the 4 MB per-XCD L2 instead of the LLC.
-  // The default round-robin dispatch interleaves ~8 heads per XCD (8 MB of
-  // K/V) and thrashes it.
-  int bh, qtile;
-  if (xcd_map) {
-    const int T = gridDim.x;  // 1-D launch
-    const int x = blockIdx.x & 7, pos = blockIdx.x >> 3;
-    const int q8 = T >> 3, r = T & 7;
-    const int pair = (x < r ? x * (q8 + 1) : r * (q8 + 1) + (x - r) * q8) + pos;
-    bh = pair / n_qt;
-    qtile = pair - bh * n_qt;
-  } else {
-    bh = blockIdx.y;
-    qtile = blockIdx.x;
-  }
+  const int bh = blockIdx.y;
+  const int qtile = blockIdx.x;
   const int b = bh / H, h = bh % H;
   const int q0 = qtile * QTILE;
   const int tid = threadIdx.x;
@@ -292,23 +280,6 @@ extern "C" void airtc_attention(const uint16_t* q, const uint16_t* k,
                                 long q_row, long k_sb, long k_sh, long k_row,
                                 long o_sb, long o_sh, long o_row, float scale,
                                 hipStream_t s) {
-  // QF=2 (128-row q-tiles) halves the K/V re-read traffic — the dominant
-  // cost for long self-attention (each q-tile block streams the whole K/V);
-  // keep QF=1 for short Lq so the grid still fills the chip.
-  static int qf_force = -2;
-  if (qf_force == -2) {
-    const char* e = getenv("AIRTC_ATTN_QF");
-    qf_force = e ? atoi(e) : 0;
-  }
-  // QF=2 measured SLOWER end-to-end (112.4 vs 118.7 fps same-box A/B):
-  // the doubled accumulator/S-fragment footprint costs more occupancy than
-  // the halved K/V traffic saves (K/V is LLC-resident at SD sizes). QF=1
-  // stays the default; the template is kept for larger-context models.
-  static int xcd_map_env = -1;
-  if (xcd_map_env < 0) {
-    const char* e = getenv("AIRTC_ATTN_XCD");
-    xcd_map_env = e ? atoi(e) : 0;
-  }
   // KVT=128 tiles: half the barriers and m/l bookkeeping per key. Measured
   // (same-box A/B): L4096 B=1 115->92.5us (+25%), B=8 479->454us (+5.5%);
   // L1024 +24%/+4%; L256 B=8 regresses 7% (occupancy cliff bites when the
@@ -320,35 +291,26 @@ extern "C" void airtc_attention(const uint16_t* q, const uint16_t* k,
     kvt_env = e ? atoi(e) : 0;  // 0 = auto
   }
   const int kvt_sel = kvt_env ? kvt_env : (Lk >= 1024 ? 128 : 64);
-  int qf = 1;
-  if (qf_force > 0) qf = qf_force;
-  const int n_qt = ceil_div(Lq, 64 * qf);
-  const int xm = xcd_map_env ? 1 : 0;
-  dim3 grid = xm ? dim3(n_qt * B * H) : dim3(n_qt, B * H);
+  dim3 grid(ceil_div(Lq, QT), B * H);
   const f16* qp = reinterpret_cast<const f16*>(q);
   const f16* kp = reinterpret_cast<const f16*>(k);
   const f16* vp = reinterpret_cast<const f16*>(v);
   f16* op = reinterpret_cast<f16*>(out);
-#define LAUNCH_T(D, QF, KT)                                                 \
-  hipLaunchKernelGGL((attention_kernel<D, QF, KT>), grid, dim3(256), 0, s,  \
-                     qp, kp, vp, op, H, Lq, Lk, q_sb, q_sh, q_row, k_sb,    \
-                     k_sh, k_row, o_sb, o_sh, o_row, scale, n_qt, xm)
-#define LAUNCH(D, QF)                                                       \
+#define LAUNCH_T(D, KT)                                                     \
+  hipLaunchKernelGGL((attention_kernel<D, KT>), grid, dim3(256), 0, s, qp,  \
+                     kp, vp, op, H, Lq, Lk, q_sb, q_sh, q_row, k_sb, k_sh,  \
+                     k_row, o_sb, o_sh, o_row, scale)
+#define LAUNCH(D)                                                           \
   do {                                                                      \
-    if (QF == 1 && kvt_sel == 128 && Lk >= 128) LAUNCH_T(D, 1, 128);        \
-    else LAUNCH_T(D, QF, 64);                                               \
+    if (kvt_sel == 128 && Lk >= 128) LAUNCH_T(D, 128);                      \
+    else LAUNCH_T(D, 64);                                                   \
   } while (0)
-  switch (d * 10 + qf) {
-    case 321: LAUNCH(32, 1); break;
-    case 322: LAUNCH(32, 2); break;
-    case 641: LAUNCH(64, 1); break;
-    case 642: LAUNCH(64, 2); break;
-    case 961: LAUNCH(96, 1); break;
-    case 962: LAUNCH(96, 2); break;
-    case 1281: LAUNCH(128, 1); break;
-    case 1282: LAUNCH(128, 2); break;
-    case 1601: LAUNCH(160, 1); break;
-    case 1602: LAUNCH(160, 2); break;
+  switch (d) {
+    case 32: LAUNCH(32); break;
+    case 64: LAUNCH(64); break;
+    case 96: LAUNCH(96); break;
+    case 128: LAUNCH(128); break;
+    case 160: LAUNCH(160); break;
     default: break;  // host wrapper guarantees one of the above
   }
 #undef LAUNCH

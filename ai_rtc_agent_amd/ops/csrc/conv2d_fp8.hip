@@ -163,16 +163,6 @@ __device__ __forceinline__ uint8_t q8_of(float v, float out_inv) {
   return (uint8_t)(p & 0xFF);
 }
 
-// XCD-aware mapping shared with conv2d.hip (same dispatcher law)
-__device__ __forceinline__ void xcd_tile_map8(int wg, int nwg, int n_tiles,
-                                              int* mt, int* nt) {
-  const int x = wg & 7, pos = wg >> 3;
-  const int q = nwg >> 3, r = nwg & 7;
-  const int wgid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + pos;
-  *nt = wgid % n_tiles;
-  *mt = wgid / n_tiles;
-}
-
 // ---------------------------------------------------------------------------
 // MFRAG = 4 (BM=128) or 2 (BM=64); BN fixed 64 (NFRAG=2), 4 waves as 2x2.
 // Requires IC % 64 == 0 (every 64-aligned K run sits inside one (r,s) tap)
@@ -197,18 +187,12 @@ __global__ __launch_bounds__(256) void conv2d_mfma_fp8_kernel(
 
   const int M = HO * WO;
   const int n_tiles = ceil_div_dev(OC, BN8);
-  int mt, nt;
-  if (splitk > 0)
-    xcd_tile_map8(blockIdx.x, gridDim.x, n_tiles, &mt, &nt);
-  else {
-    mt = blockIdx.x / n_tiles;
-    nt = blockIdx.x - mt * n_tiles;
-  }
-  const int spk = splitk > 0 ? splitk : -splitk;
+  const int mt = blockIdx.x / n_tiles;
+  const int nt = blockIdx.x - mt * n_tiles;
   const int m0 = mt * BM;
   const int n0 = nt * BN8;
-  const int b = blockIdx.z / spk;
-  const int split = blockIdx.z - b * spk;
+  const int b = blockIdx.z / splitk;
+  const int split = blockIdx.z - b * splitk;
   const XT* xb = x + (long)b * H * W * IC;
   const float* affb = in_aff ? in_aff + (long)b * IC * 2 : nullptr;
   const float inv_sa = 1.0f / sa;  // encode multiplies; clamp at +-448
@@ -246,7 +230,7 @@ __global__ __launch_bounds__(256) void conv2d_mfma_fp8_kernel(
     for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = {0.f, 0.f, 0.f, 0.f};
 
   const int nk = ceil_div_dev(K, BK8);
-  const int per = (nk + spk - 1) / spk;
+  const int per = (nk + splitk - 1) / splitk;
   const int k_lo = split * per;
   const int k_hi = min(nk, k_lo + per);
 
@@ -325,7 +309,7 @@ __global__ __launch_bounds__(256) void conv2d_mfma_fp8_kernel(
     compute_tile();
   }
 
-  if (spk == 1) {
+  if (splitk == 1) {
     f16* ob = out + (long)b * M * OC;
     uint8_t* oq = out_q8 ? out_q8 + (long)b * M * OC : nullptr;
     const long cb_off = (long)b * OC;
@@ -353,7 +337,7 @@ __global__ __launch_bounds__(256) void conv2d_mfma_fp8_kernel(
   } else {
     // pre-dequantized f32 slab: the shared finalize pass then applies the
     // bias/residual/act epilogue with no fp8 knowledge
-    float* wsb = ws + ((long)b * spk + split) * M * OC;
+    float* wsb = ws + ((long)b * splitk + split) * M * OC;
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) {
       const int col = n0 + wn * 32 + ni * 16 + (lane & 15);
@@ -409,12 +393,10 @@ extern "C" void airtc_conv2d_fp8_mfma(
   const float* b1 = splitk == 1 ? bias : nullptr;
   const f16* cb1 = splitk == 1 ? cb : nullptr;
   const f16* res1 = splitk == 1 ? res : nullptr;
-  // tile mapping selection mirrors conv2d.hip (XCD map env-gated there;
-  // fp8 uses the measured default = plain mapping, sign encodes it)
 #define FP8_LAUNCH(MF, XT, XP)                                                \
   hipLaunchKernelGGL((conv2d_mfma_fp8_kernel<MF, XT>), grid, dim3(256), 0, s, \
                      XP, w_fp8, dq, b1, cb1, res1, op, ws, H, W, IC, HO, WO,  \
-                     OC, R, S, stride, pad, act, K, -splitk, in_aff, in_act,  \
+                     OC, R, S, stride, pad, act, K, splitk, in_aff, in_act,   \
                      a_scale, splitk == 1 ? out_q8 : nullptr, out_inv)
   if (x_is_q8) {
     const uint8_t* xq = reinterpret_cast<const uint8_t*>(x);

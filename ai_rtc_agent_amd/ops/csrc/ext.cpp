@@ -37,9 +37,8 @@ torch::Tensor conv2d_impl(torch::Tensor x, torch::Tensor w_perm,
                           c10::optional<torch::Tensor> residual, int64_t R,
                           int64_t S, int64_t stride, int64_t pad, int64_t act,
                           c10::optional<torch::Tensor> in_affine,
-                          int64_t in_act,
-                          c10::optional<torch::Tensor> counters,
-                          int64_t stats_groups, torch::Tensor* gn_part) {
+                          int64_t in_act, int64_t stats_groups,
+                          torch::Tensor* gn_part) {
   CHECK_IN(x);
   CHECK_IN(w_perm);
   TORCH_CHECK(x.dtype() == torch::kHalf && w_perm.dtype() == torch::kHalf);
@@ -83,20 +82,11 @@ torch::Tensor conv2d_impl(torch::Tensor x, torch::Tensor w_perm,
   }
   float* wsp = nullptr;
   torch::Tensor ws;
-  const int splitk = path == 100 ? 1 : (path > 0 ? path : -path);
+  const int splitk = path > 0 ? path : -path;
   if (splitk > 1) {
     ws = torch::empty({(long)B * splitk, (long)HO * WO, OC},
                       x.options().dtype(torch::kFloat));
     wsp = ws.data_ptr<float>();
-  }
-  int* cnt = nullptr;
-  if (counters.has_value() && splitk > 1) {
-    CHECK_IN((*counters));
-    TORCH_CHECK(counters->dtype() == torch::kInt, "counters must be int32");
-    TORCH_CHECK(counters->numel() >= (long)B * ((HO * WO + 63) / 64) *
-                                         ((OC + 63) / 64),
-                "counters buffer too small");
-    cnt = counters->data_ptr<int>();
   }
   float* gnp = nullptr;
   if (gn_part && stats_groups > 0 && aligned16(bp) && aligned16(cb) &&
@@ -112,7 +102,7 @@ torch::Tensor conv2d_impl(torch::Tensor x, torch::Tensor w_perm,
   const int wrote = airtc_conv2d_mfma(
       h_ptr(x), h_ptr(w_perm), bp, cb, res, h_ptr_mut(out), wsp, B, H, W, IC,
       HO, WO, OC, (int)R, (int)S, (int)stride, (int)pad, (int)act, path, aff,
-      (int)in_act, cnt, gnp, (int)stats_groups, cur_stream());
+      (int)in_act, gnp, (int)stats_groups, cur_stream());
   // the launcher has the last word: partials it did not write are dropped,
   // and the consumer norm runs its own statistics pass
   if (gnp && !wrote) *gn_part = torch::Tensor();
@@ -124,10 +114,9 @@ torch::Tensor conv2d(torch::Tensor x, torch::Tensor w_perm,
                      c10::optional<torch::Tensor> cbias,
                      c10::optional<torch::Tensor> residual, int64_t R,
                      int64_t S, int64_t stride, int64_t pad, int64_t act,
-                     c10::optional<torch::Tensor> in_affine, int64_t in_act,
-                     c10::optional<torch::Tensor> counters) {
+                     c10::optional<torch::Tensor> in_affine, int64_t in_act) {
   return conv2d_impl(x, w_perm, bias, cbias, residual, R, S, stride, pad, act,
-                     in_affine, in_act, counters, 0, nullptr);
+                     in_affine, in_act, 0, nullptr);
 }
 
 // conv2d + GroupNorm partials for the consumer norm: (out, partials | None)
@@ -138,13 +127,10 @@ pybind11::tuple conv2d_stats(torch::Tensor x, torch::Tensor w_perm,
                              int64_t S, int64_t stride, int64_t pad,
                              int64_t act,
                              c10::optional<torch::Tensor> in_affine,
-                             int64_t in_act,
-                             c10::optional<torch::Tensor> counters,
-                             int64_t stats_groups) {
+                             int64_t in_act, int64_t stats_groups) {
   torch::Tensor part;
   auto out = conv2d_impl(x, w_perm, bias, cbias, residual, R, S, stride, pad,
-                         act, in_affine, in_act, counters, stats_groups,
-                         &part);
+                         act, in_affine, in_act, stats_groups, &part);
   if (part.defined()) return pybind11::make_tuple(out, part);
   return pybind11::make_tuple(out, pybind11::none());
 }
@@ -177,59 +163,54 @@ int check_partials(const torch::Tensor& p, int B, int64_t groups) {
   return (int)p.size(1);
 }
 
-torch::Tensor group_norm_silu_fp8(torch::Tensor x, int64_t groups,
-                                  torch::Tensor gamma, torch::Tensor beta,
-                                  double eps, int64_t act, double a_scale,
-                                  c10::optional<torch::Tensor> partials) {
+// GroupNorm + act into out (f16, or u8 e4m3 codes at a_scale): on the
+// producer's partials when given, else after an own statistics pass
+torch::Tensor group_norm_into(const torch::Tensor& x, torch::Tensor out,
+                              int64_t groups, const torch::Tensor& gamma,
+                              const torch::Tensor& beta, double eps,
+                              int64_t act, double a_scale,
+                              const c10::optional<torch::Tensor>& partials) {
   CHECK_IN(x);
   TORCH_CHECK(x.dtype() == torch::kHalf);
   const int B = x.size(0);
   const int C = x.size(-1);
   const long HW = x.numel() / ((long)B * C);
-  auto out = torch::empty_like(x, x.options().dtype(torch::kUInt8));
+  const bool q8 = out.dtype() == torch::kUInt8;
+  const float* part = nullptr;
+  int npart = 0;
+  torch::Tensor ws;
+  float* wsp = nullptr;
   if (partials.has_value()) {
-    const int npart = check_partials(*partials, B, groups);
-    airtc_group_norm_apply(h_ptr(x), partials->data_ptr<float>(), npart,
-                           gamma.data_ptr<float>(), beta.data_ptr<float>(),
-                           nullptr, out.data_ptr<uint8_t>(), B, (int)HW, C,
-                           (int)groups, (float)eps, (int)act, (float)a_scale,
-                           cur_stream());
-    return out;
+    npart = check_partials(*partials, B, groups);
+    part = partials->data_ptr<float>();
+  } else {
+    ws = torch::empty({(long)B * groups * AIRTC_GN_MAX_PART * 2},
+                      x.options().dtype(torch::kFloat));
+    wsp = ws.data_ptr<float>();
   }
-  auto ws = torch::empty({(long)B * groups * AIRTC_GN_MAX_PART * 2},
-                         x.options().dtype(torch::kFloat));
-  airtc_group_norm_silu_fp8(h_ptr(x), gamma.data_ptr<float>(),
-                            beta.data_ptr<float>(), out.data_ptr<uint8_t>(),
-                            ws.data_ptr<float>(), B, (int)HW, C, (int)groups,
-                            (float)eps, (int)act, (float)a_scale,
-                            cur_stream());
+  airtc_group_norm(h_ptr(x), part, npart, gamma.data_ptr<float>(),
+                   beta.data_ptr<float>(), q8 ? nullptr : h_ptr_mut(out),
+                   q8 ? out.data_ptr<uint8_t>() : nullptr, wsp, B, (int)HW, C,
+                   (int)groups, (float)eps, (int)act, (float)a_scale,
+                   cur_stream());
   return out;
+}
+
+torch::Tensor group_norm_silu_fp8(torch::Tensor x, int64_t groups,
+                                  torch::Tensor gamma, torch::Tensor beta,
+                                  double eps, int64_t act, double a_scale,
+                                  c10::optional<torch::Tensor> partials) {
+  auto out = torch::empty_like(x, x.options().dtype(torch::kUInt8));
+  return group_norm_into(x, out, groups, gamma, beta, eps, act, a_scale,
+                         partials);
 }
 
 torch::Tensor group_norm_silu(torch::Tensor x, int64_t groups,
                               torch::Tensor gamma, torch::Tensor beta,
                               double eps, int64_t act,
                               c10::optional<torch::Tensor> partials) {
-  CHECK_IN(x);
-  const int B = x.size(0);
-  const int C = x.size(-1);
-  const long HW = x.numel() / ((long)B * C);
-  auto out = torch::empty_like(x);
-  if (partials.has_value()) {
-    const int npart = check_partials(*partials, B, groups);
-    airtc_group_norm_apply(h_ptr(x), partials->data_ptr<float>(), npart,
-                           gamma.data_ptr<float>(), beta.data_ptr<float>(),
-                           h_ptr_mut(out), nullptr, B, (int)HW, C, (int)groups,
-                           (float)eps, (int)act, 1.0f, cur_stream());
-    return out;
-  }
-  auto ws = torch::empty({(long)B * groups * AIRTC_GN_MAX_PART * 2},
-                         x.options().dtype(torch::kFloat));
-  airtc_group_norm_silu(h_ptr(x), gamma.data_ptr<float>(),
-                        beta.data_ptr<float>(), h_ptr_mut(out),
-                        ws.data_ptr<float>(), B, (int)HW, C, (int)groups,
-                        (float)eps, (int)act, cur_stream());
-  return out;
+  return group_norm_into(x, torch::empty_like(x), groups, gamma, beta, eps,
+                         act, 1.0, partials);
 }
 
 torch::Tensor layer_norm(torch::Tensor x, torch::Tensor gamma,
@@ -557,7 +538,7 @@ torch::Tensor conv2d_fp8(torch::Tensor x, torch::Tensor w_fp8,
   const int HO = (H + 2 * (int)pad - (int)R) / (int)stride + 1;
   const int WO = (W + 2 * (int)pad - (int)S) / (int)stride + 1;
   int path0 = airtc_conv2d_splitk_for(B, HO, WO, OC, IC);
-  if (path0 == 0 || path0 == 100) path0 = HO * WO >= 2048 ? 1 : -1;
+  if (path0 == 0) path0 = HO * WO >= 2048 ? 1 : -1;
   const int splitk0 = path0 > 0 ? path0 : -path0;
   // q8 output only on the split-K-free path (the finalize pass stays
   // fp8-agnostic); callers get f16 back otherwise and must dispatch on
@@ -664,8 +645,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("cbias"), pybind11::arg("residual"), pybind11::arg("R"),
         pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"),
         pybind11::arg("act"), pybind11::arg("in_affine") = pybind11::none(),
-        pybind11::arg("in_act") = 0,
-        pybind11::arg("counters") = pybind11::none());
+        pybind11::arg("in_act") = 0);
   m.def("conv2d_stats", &conv2d_stats,
         "conv2d that also returns GroupNorm partials of its output for a "
         "consumer norm with stats_groups groups: (out, partials | None)",
@@ -673,8 +653,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("cbias"), pybind11::arg("residual"), pybind11::arg("R"),
         pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"),
         pybind11::arg("act"), pybind11::arg("in_affine"),
-        pybind11::arg("in_act"), pybind11::arg("counters"),
-        pybind11::arg("stats_groups"));
+        pybind11::arg("in_act"), pybind11::arg("stats_groups"));
   m.def("group_norm_silu", &group_norm_silu, pybind11::arg("x"),
         pybind11::arg("groups"), pybind11::arg("gamma"), pybind11::arg("beta"),
         pybind11::arg("eps"), pybind11::arg("act"),

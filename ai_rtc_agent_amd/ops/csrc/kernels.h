@@ -44,28 +44,21 @@ void airtc_sched_blend(const uint16_t* xt, const uint16_t* eps,
 // B*G*AIRTC_GN_MAX_PART*2 floats always fits.
 #define AIRTC_GN_MAX_PART 64
 int airtc_group_norm_nchunk(int B, int G);
-// apply only, on partials from another producer (the split-K finalize with
-// gn_part below); exactly one of out / out_q8 is non-null
-void airtc_group_norm_apply(const uint16_t* x, const float* part, int npart,
-                            const float* gamma, const float* beta,
-                            uint16_t* out, uint8_t* out_q8, int B, int HW,
-                            int C, int G, float eps, int act, float a_scale,
-                            hipStream_t s);
-// ws for the three launchers below: B*G*AIRTC_GN_MAX_PART*2 floats
-void airtc_group_norm_silu(const uint16_t* x, const float* gamma,
-                           const float* beta, uint16_t* out, float* ws, int B,
-                           int HW, int C, int G, float eps, int act,
-                           hipStream_t s);
+// GroupNorm + act. part == nullptr: the statistics pass runs first, into ws
+// (B*G*AIRTC_GN_MAX_PART*2 floats). Otherwise apply only, on npart partials
+// from another producer (the split-K finalize with gn_part below); ws is
+// unused. Exactly one of out / out_q8 is non-null: f16 result, or e4m3
+// codes q = clamp(act(gn(x)) / a_scale) (producer-side quantization for the
+// fp8 conv path).
+void airtc_group_norm(const uint16_t* x, const float* part, int npart,
+                      const float* gamma, const float* beta, uint16_t* out,
+                      uint8_t* out_q8, float* ws, int B, int HW, int C, int G,
+                      float eps, int act, float a_scale, hipStream_t s);
 void airtc_layer_norm(const uint16_t* x, const float* gamma, const float* beta,
                       uint16_t* out, long rows, int C, float eps,
                       hipStream_t s);
-// fp8-output GN: apply pass writes e4m3 codes q = clamp(act(gn(x))/a_scale)
-// (producer-side quantization for the fp8 conv path)
-void airtc_group_norm_silu_fp8(const uint16_t* x, const float* gamma,
-                               const float* beta, uint8_t* out, float* ws,
-                               int B, int HW, int C, int G, float eps,
-                               int act, float a_scale, hipStream_t s);
-// (B, C, 2) f32 affine pairs for the fused GN->conv input transform
+// (B, C, 2) f32 affine pairs for the fused GN->conv input transform; ws as
+// above
 void airtc_group_norm_coeffs(const uint16_t* x, const float* gamma,
                              const float* beta, float* coeffs, float* ws,
                              int B, int HW, int C, int G, float eps,
@@ -77,8 +70,9 @@ void airtc_group_norm_coeffs(const uint16_t* x, const float* gamma,
 // cbias: optional per-(batch, out-channel) f16 bias (B, OC) — time-emb add
 // residual: optional f16 tensor with out's shape, added pre-activation
 // out : (B, HO, WO, OC) f16
-// path: from airtc_conv2d_splitk_for (0=direct, 1=BM128, -k=BM64 splitk k);
-// ws  : f32 workspace (B*k, HO*WO, OC) required when path < -1
+// path: from airtc_conv2d_splitk_for (0 = direct, +k = BM128 split-K k,
+//       -k = BM64 split-K k);
+// ws  : f32 workspace (B*k, HO*WO, OC) required when k > 1
 int airtc_conv2d_splitk_for(int B, int HO, int WO, int OC, int IC);
 // in_aff: optional (B, IC, 2) f32 per-channel input affine (fused GN) with
 // in_act applied after — transforms x AT LOAD TIME (padding stays zero)
@@ -89,8 +83,8 @@ int airtc_conv2d_mfma(const uint16_t* x, const uint16_t* w, const float* bias,
                       uint16_t* out, float* ws, int B, int H, int W, int IC,
                       int HO, int WO, int OC, int R, int S, int stride,
                       int pad, int act, int path, const float* in_aff,
-                      int in_act, int* counters, float* gn_part,
-                      int gn_groups, hipStream_t s);
+                      int in_act, float* gn_part, int gn_groups,
+                      hipStream_t s);
 // gn_part: optional GroupNorm partials of the OUTPUT for a consumer norm
 // with gn_groups groups (layout above), written by the split-K finalize from
 // the rounded f16 values. Pass it only when airtc_conv2d_stats_nchunk
@@ -113,7 +107,7 @@ void airtc_conv2d_direct(const uint16_t* x, const uint16_t* w,
 // staging loads (a_scale). Requires IC % 64 == 0; path from
 // airtc_conv2d_splitk_for (nonzero).
 // x_is_q8: x already holds e4m3 codes (u8, producer-quantized by e.g.
-// airtc_group_norm_silu_fp8) — staging is a raw byte copy, in_aff unused.
+// airtc_group_norm with out_q8) — staging is a raw byte copy, in_aff unused.
 // out_q8/out_inv: when non-null and split-K == 1, the epilogue writes e4m3
 // codes q = e4m3(clamp(v / out_scale)) instead of f16 (chained fp8 layers).
 void airtc_conv2d_fp8_mfma(const uint16_t* x, const uint8_t* w_fp8,

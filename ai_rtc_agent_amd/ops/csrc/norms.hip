@@ -64,62 +64,32 @@ __global__ void group_norm_stats_kernel(const f16* __restrict__ x,
   }
 }
 
-__global__ void group_norm_apply_kernel(const f16* __restrict__ x,
-                                        const float* __restrict__ ws,
-                                        const float* __restrict__ gamma,
-                                        const float* __restrict__ beta,
-                                        f16* __restrict__ out, int HW, int C,
-                                        int G, int nchunk, float eps,
-                                        int act) {
-  const int chunk = blockIdx.y;
-  const int b = blockIdx.x / G;
-  const int g = blockIdx.x % G;
-  const int Cg = C / G;
-  const int Cg2 = Cg / 2;
-  const long base = (long)b * HW * C + (long)g * Cg;
-
-  // fold the tiny cross-chunk reduction into every block (nchunk <= 64)
-  __shared__ float stats[2];
-  if (threadIdx.x == 0) {
-    const float* w = &ws[(long)blockIdx.x * nchunk * 2];
-    float s0 = 0.f, s1 = 0.f;
-    for (int i = 0; i < nchunk; ++i) { s0 += w[2 * i]; s1 += w[2 * i + 1]; }
-    const float n = (float)HW * Cg;
-    const float mean = s0 / n;
-    stats[0] = mean;
-    stats[1] = rsqrtf(s1 / n - mean * mean + eps);
-  }
-  __syncthreads();
-  const float mean = stats[0], rstd = stats[1];
-
-  long lo, hi;
-  gn_chunk_range((long)HW * Cg2, chunk, nchunk, &lo, &hi);
-  for (long i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-    long p = i / Cg2, c2 = i - p * Cg2;
-    long idx = base + p * C + c2 * 2;
-    f16x2 v = *reinterpret_cast<const f16x2*>(&x[idx]);
-    int ch = g * Cg + (int)c2 * 2;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      float t = ((float)v[j] - mean) * rstd * gamma[ch + j] + beta[ch + j];
-      v[j] = (f16)apply_act(t, act);
-    }
-    *reinterpret_cast<f16x2*>(&out[idx]) = v;
-  }
+// fold npart (sum, sumsq) partials, in index order, into the (mean, rstd) of
+// a group of n elements (npart <= AIRTC_GN_MAX_PART: tiny, so every consumer
+// block repeats it in its prologue instead of a separate launch)
+__device__ __forceinline__ void gn_fold_partials(const float* w, int npart,
+                                                 float n, float eps,
+                                                 float* mean_out,
+                                                 float* rstd_out) {
+  float s0 = 0.f, s1 = 0.f;
+  for (int i = 0; i < npart; ++i) { s0 += w[2 * i]; s1 += w[2 * i + 1]; }
+  const float mean = s0 / n;
+  *mean_out = mean;
+  *rstd_out = rsqrtf(s1 / n - mean * mean + eps);
 }
 
-// fp8-output variant: the apply pass writes OCP e4m3 CODES (q = clamp(
-// act(gn(x)) * inv_sa, +-448)) so the fp8 conv stages raw bytes with zero
-// encode VALU and half the activation HBM traffic (producer-side
-// quantization — the conv's inline encode would otherwise re-encode every
-// element once per 3x3 tap). Encode uses the non-scaled v_cvt_pk_fp8_f32
-// (the scalef32 forms round up a ULP at arbitrary scales — see
-// conv2d_fp8.hip header).
-__global__ void group_norm_apply_fp8_kernel(
+// Q8: the apply pass writes OCP e4m3 CODES (q = clamp(act(gn(x)) * inv_sa,
+// +-448)) instead of f16, so the fp8 conv stages raw bytes with zero encode
+// VALU and half the activation HBM traffic (producer-side quantization — the
+// conv's inline encode would otherwise re-encode every element once per 3x3
+// tap). Encode uses the non-scaled v_cvt_pk_fp8_f32 (the scalef32 forms
+// round up a ULP at arbitrary scales — see conv2d_fp8.hip header).
+template <bool Q8>
+__global__ void group_norm_apply_kernel(
     const f16* __restrict__ x, const float* __restrict__ ws,
     const float* __restrict__ gamma, const float* __restrict__ beta,
-    uint8_t* __restrict__ out, int HW, int C, int G, int nchunk, float eps,
-    int act, float inv_sa) {
+    f16* __restrict__ out, uint8_t* __restrict__ outq, int HW, int C, int G,
+    int nchunk, float eps, int act, float inv_sa) {
   const int chunk = blockIdx.y;
   const int b = blockIdx.x / G;
   const int g = blockIdx.x % G;
@@ -128,15 +98,9 @@ __global__ void group_norm_apply_fp8_kernel(
   const long base = (long)b * HW * C + (long)g * Cg;
 
   __shared__ float stats[2];
-  if (threadIdx.x == 0) {
-    const float* w = &ws[(long)blockIdx.x * nchunk * 2];
-    float s0 = 0.f, s1 = 0.f;
-    for (int i = 0; i < nchunk; ++i) { s0 += w[2 * i]; s1 += w[2 * i + 1]; }
-    const float n = (float)HW * Cg;
-    const float mean = s0 / n;
-    stats[0] = mean;
-    stats[1] = rsqrtf(s1 / n - mean * mean + eps);
-  }
+  if (threadIdx.x == 0)
+    gn_fold_partials(&ws[(long)blockIdx.x * nchunk * 2], nchunk,
+                     (float)HW * Cg, eps, &stats[0], &stats[1]);
   __syncthreads();
   const float mean = stats[0], rstd = stats[1];
 
@@ -151,10 +115,19 @@ __global__ void group_norm_apply_fp8_kernel(
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       float t = ((float)v[j] - mean) * rstd * gamma[ch + j] + beta[ch + j];
-      a[j] = fminf(fmaxf(apply_act(t, act) * inv_sa, -448.0f), 448.0f);
+      a[j] = apply_act(t, act);
     }
-    int p2 = __builtin_amdgcn_cvt_pk_fp8_f32(a[0], a[1], 0, false);
-    *reinterpret_cast<short*>(&out[idx]) = (short)(p2 & 0xFFFF);
+    if (Q8) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        a[j] = fminf(fmaxf(a[j] * inv_sa, -448.0f), 448.0f);
+      int p2 = __builtin_amdgcn_cvt_pk_fp8_f32(a[0], a[1], 0, false);
+      *reinterpret_cast<short*>(&outq[idx]) = (short)(p2 & 0xFFFF);
+    } else {
+      v[0] = (f16)a[0];
+      v[1] = (f16)a[1];
+      *reinterpret_cast<f16x2*>(&out[idx]) = v;
+    }
   }
 }
 
@@ -254,7 +227,7 @@ __global__ __launch_bounds__(256) void group_norm_stats_v8_kernel(
   }
 }
 
-// Q8: write e4m3 codes (see group_norm_apply_fp8_kernel) instead of f16
+// Q8: write e4m3 codes (see group_norm_apply_kernel) instead of f16
 template <bool Q8>
 __global__ __launch_bounds__(256) void group_norm_apply_v8_kernel(
     const f16* __restrict__ x, const float* __restrict__ part,
@@ -273,13 +246,9 @@ __global__ __launch_bounds__(256) void group_norm_apply_v8_kernel(
   // fold the tiny cross-chunk reduction into every block (npart <= 64)
   if ((int)threadIdx.x < gpt) {
     const int g = blockIdx.y * gpt + threadIdx.x;
-    const float* w = &part[((long)b * G + g) * npart * 2];
-    float s0 = 0.f, s1 = 0.f;
-    for (int i = 0; i < npart; ++i) { s0 += w[2 * i]; s1 += w[2 * i + 1]; }
-    const float n = (float)HW * Cg;
-    const float mean = s0 / n;
-    gst[0][threadIdx.x] = mean;
-    gst[1][threadIdx.x] = rsqrtf(s1 / n - mean * mean + eps);
+    gn_fold_partials(&part[((long)b * G + g) * npart * 2], npart,
+                     (float)HW * Cg, eps, &gst[0][threadIdx.x],
+                     &gst[1][threadIdx.x]);
   }
   __syncthreads();
   for (int c = threadIdx.x; c < cw; c += 256) {
@@ -386,18 +355,9 @@ __global__ void group_norm_coeffs_kernel(const float* __restrict__ ws,
   const int g = blockIdx.x % G;
   const int Cg = C / G;
   __shared__ float stats[2];
-  if (threadIdx.x == 0) {
-    const float* w = &ws[(long)blockIdx.x * nchunk * 2];
-    float s0 = 0.f, s1 = 0.f;
-    for (int i = 0; i < nchunk; ++i) {
-      s0 += w[2 * i];
-      s1 += w[2 * i + 1];
-    }
-    const float n = (float)HW * Cg;
-    const float mean = s0 / n;
-    stats[0] = mean;
-    stats[1] = rsqrtf(s1 / n - mean * mean + eps);
-  }
+  if (threadIdx.x == 0)
+    gn_fold_partials(&ws[(long)blockIdx.x * nchunk * 2], nchunk,
+                     (float)HW * Cg, eps, &stats[0], &stats[1]);
   __syncthreads();
   const float mean = stats[0], rstd = stats[1];
   for (int c = threadIdx.x; c < Cg; c += blockDim.x) {
@@ -421,43 +381,34 @@ extern "C" void airtc_group_norm_coeffs(const uint16_t* x, const float* gamma,
                      ws, gamma, beta, coeffs, HW, C, G, nchunk, eps);
 }
 
-extern "C" void airtc_group_norm_silu(const uint16_t* x, const float* gamma,
-                                      const float* beta, uint16_t* out,
-                                      float* ws, int B, int HW, int C, int G,
-                                      float eps, int act, hipStream_t s) {
-  const f16* xp = reinterpret_cast<const f16*>(x);
-  GnPlan pl;
-  if (gn_fast_ok(x, out, B, C, G, &pl)) {
-    const int npart = gn_launch_stats_v8(pl, xp, ws, B, HW, C, G, s);
-    gn_launch_apply_v8(pl, xp, ws, npart, gamma, beta,
-                       reinterpret_cast<f16*>(out), nullptr, B, HW, C, G, eps,
-                       act, 0.f, s);
-    return;
-  }
-  const int nchunk = airtc_group_norm_nchunk(B, G);
-  dim3 grid(B * G, nchunk);
-  hipLaunchKernelGGL(group_norm_stats_kernel, grid, dim3(256), 0, s, xp, ws,
-                     HW, C, G, nchunk);
-  hipLaunchKernelGGL(group_norm_apply_kernel, grid, dim3(256), 0, s, xp, ws,
-                     gamma, beta, reinterpret_cast<f16*>(out), HW, C, G,
-                     nchunk, eps, act);
-}
-
-// Apply only, on partial statistics somebody else produced (the split-K
-// finalize, conv2d.hip): part is [B*G][npart][2], npart <= 64. Exactly one
-// of out / out_q8 is non-null (f16 result, or e4m3 codes at a_scale).
-extern "C" void airtc_group_norm_apply(const uint16_t* x, const float* part,
-                                       int npart, const float* gamma,
-                                       const float* beta, uint16_t* out,
-                                       uint8_t* out_q8, int B, int HW, int C,
-                                       int G, float eps, int act,
-                                       float a_scale, hipStream_t s) {
+// GroupNorm + act, the one launcher. part == nullptr: run the statistics pass
+// into ws first; otherwise apply on partial statistics somebody else produced
+// (the split-K finalize, conv2d.hip): part is [B*G][npart][2], npart <= 64.
+// Exactly one of out / out_q8 is non-null (f16 result, or e4m3 codes at
+// a_scale).
+extern "C" void airtc_group_norm(const uint16_t* x, const float* part,
+                                 int npart, const float* gamma,
+                                 const float* beta, uint16_t* out,
+                                 uint8_t* out_q8, float* ws, int B, int HW,
+                                 int C, int G, float eps, int act,
+                                 float a_scale, hipStream_t s) {
   const f16* xp = reinterpret_cast<const f16*>(x);
   f16* op = reinterpret_cast<f16*>(out);
   const float inv_sa = out_q8 ? 1.0f / a_scale : 0.f;
   GnPlan pl;
-  if (gn_fast_ok(x, out_q8 ? (const void*)out_q8 : (const void*)out, B, C, G,
-                 &pl)) {
+  const bool fast = gn_fast_ok(
+      x, out_q8 ? (const void*)out_q8 : (const void*)out, B, C, G, &pl);
+  if (!part) {
+    if (fast) {
+      npart = gn_launch_stats_v8(pl, xp, ws, B, HW, C, G, s);
+    } else {
+      npart = airtc_group_norm_nchunk(B, G);
+      hipLaunchKernelGGL(group_norm_stats_kernel, dim3(B * G, npart),
+                         dim3(256), 0, s, xp, ws, HW, C, G, npart);
+    }
+    part = ws;
+  }
+  if (fast) {
     gn_launch_apply_v8(pl, xp, part, npart, gamma, beta, op, out_q8, B, HW, C,
                        G, eps, act, inv_sa, s);
     return;
@@ -465,35 +416,13 @@ extern "C" void airtc_group_norm_apply(const uint16_t* x, const float* part,
   // the f16x2 kernels chunk their own work by the partial count
   dim3 grid(B * G, npart);
   if (out_q8)
-    hipLaunchKernelGGL(group_norm_apply_fp8_kernel, grid, dim3(256), 0, s, xp,
-                       part, gamma, beta, out_q8, HW, C, G, npart, eps, act,
-                       inv_sa);
+    hipLaunchKernelGGL(group_norm_apply_kernel<true>, grid, dim3(256), 0, s,
+                       xp, part, gamma, beta, op, out_q8, HW, C, G, npart, eps,
+                       act, inv_sa);
   else
-    hipLaunchKernelGGL(group_norm_apply_kernel, grid, dim3(256), 0, s, xp,
-                       part, gamma, beta, op, HW, C, G, npart, eps, act);
-}
-
-extern "C" void airtc_group_norm_silu_fp8(const uint16_t* x,
-                                          const float* gamma,
-                                          const float* beta, uint8_t* out,
-                                          float* ws, int B, int HW, int C,
-                                          int G, float eps, int act,
-                                          float a_scale, hipStream_t s) {
-  GnPlan pl;
-  if (gn_fast_ok(x, out, B, C, G, &pl)) {
-    const f16* xp = reinterpret_cast<const f16*>(x);
-    const int npart = gn_launch_stats_v8(pl, xp, ws, B, HW, C, G, s);
-    gn_launch_apply_v8(pl, xp, ws, npart, gamma, beta, nullptr, out, B, HW, C,
-                       G, eps, act, 1.0f / a_scale, s);
-    return;
-  }
-  const int nchunk = airtc_group_norm_nchunk(B, G);
-  dim3 grid(B * G, nchunk);
-  hipLaunchKernelGGL(group_norm_stats_kernel, grid, dim3(256), 0, s,
-                     reinterpret_cast<const f16*>(x), ws, HW, C, G, nchunk);
-  hipLaunchKernelGGL(group_norm_apply_fp8_kernel, grid, dim3(256), 0, s,
-                     reinterpret_cast<const f16*>(x), ws, gamma, beta, out,
-                     HW, C, G, nchunk, eps, act, 1.0f / a_scale);
+    hipLaunchKernelGGL(group_norm_apply_kernel<false>, grid, dim3(256), 0, s,
+                       xp, part, gamma, beta, op, out_q8, HW, C, G, npart, eps,
+                       act, inv_sa);
 }
 
 // ---------------------------------------------------------------------------

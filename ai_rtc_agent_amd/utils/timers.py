@@ -1,7 +1,7 @@
 """Per-stage timers + FPS / glass-to-glass latency stats.
 
 The reference has no metrics; BASELINE.json's headline
-metric (img2img FPS + p50 glass-to-glass ms) requires first-class counters,
+metric (img2img FPS + p50 glass-to-glass ms) requires first-class metrics,
 so every pipeline stage (decode/preprocess/unet/vae/encode) reports here and
 the agent exposes them at GET /stats.
 
