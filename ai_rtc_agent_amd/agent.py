@@ -360,6 +360,12 @@ def main() -> None:
                              "contain = whole frame with black bars, "
                              "stretch = whole frame, aspect not kept "
                              "(default: $AIRTC_FIT_MODE or cover)")
+    parser.add_argument("--yuv", action="store_true",
+                        help="exchange YUV 4:2:0 (I420) frames between the "
+                             "codec and the engine instead of packed RGB: "
+                             "colour conversion runs on the GPU and the "
+                             "codec reads/writes its planes directly "
+                             "(same as AIRTC_MEDIA_YUV=1)")
     parser.add_argument("--streams-per-gpu", type=int, default=1,
                         help="multi-stream batched serving: sessions per "
                              "GPU batched through one engine (fbs=K; "
@@ -373,6 +379,10 @@ def main() -> None:
     args = parser.parse_args()
 
     logging.basicConfig(level=getattr(logging, args.log_level.upper(), logging.INFO))
+    if args.yuv:
+        # read by config.media_yuv() (codec selection, EngineConfig's
+        # output_format default) here and in spawned workers
+        os.environ["AIRTC_MEDIA_YUV"] = "1"
     ports = None
     if args.udp_ports:
         lo, _, hi = args.udp_ports.partition("-")

@@ -45,6 +45,11 @@ def _env_float(name: str, default: float) -> float:
 #                                        NVENC_* in reference docs/environment.md:17-25)
 # AIRTC_FIT_MODE (cover|contain|stretch) -> EngineConfig.fit_mode, how frames
 #                                        of another resolution are fitted
+# AIRTC_MEDIA_YUV (0|1)              -> media_yuv(): the media plane and the
+#                                        engine exchange I420 frames instead
+#                                        of packed RGB (codec plane I/O, GPU
+#                                        colour conversion); also the default
+#                                        of EngineConfig.output_format
 
 
 def engines_cache_dir() -> str:
@@ -75,6 +80,16 @@ def hw_encode_enabled() -> bool:
 
 def hw_decode_enabled() -> bool:
     return _env_bool("VCN_DEC", _env_bool("NVDEC", False))
+
+
+def media_yuv() -> bool:
+    """YUV 4:2:0 end to end (default off): decoders hand out I420 frames,
+    the engine converts them on the GPU and returns I420 for the encoder
+    (frame format: ops/interface.py)."""
+    return _env_bool("AIRTC_MEDIA_YUV", False)
+
+
+OUTPUT_FORMATS = ("rgb", "i420")
 
 
 @dataclass
@@ -158,6 +173,16 @@ class EngineConfig:
     # resize; contain = whole frame with black bars; stretch = whole frame,
     # aspect not kept. Engine-sized frames are never touched.
     fit_mode: str = field(default_factory=lambda: os.environ.get("AIRTC_FIT_MODE") or "cover")
+
+    # what the engine returns: "rgb" = (H,W,3) u8 as ever, "i420" = (3H/2,W)
+    # u8 planes ready for the codec (needs even height and width). Input
+    # frames may be either format whatever this says.
+    output_format: str = field(default_factory=lambda: "i420" if media_yuv() else "rgb")
+
+    def __post_init__(self) -> None:
+        if self.output_format not in OUTPUT_FORMATS:
+            raise ValueError(
+                f"output_format must be one of {OUTPUT_FORMATS}, got {self.output_format!r}")
 
     @property
     def denoising_steps(self) -> int:

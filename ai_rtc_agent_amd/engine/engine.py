@@ -58,6 +58,13 @@ class StreamDiffusionEngine:
         text_encoder: Optional[TextEncoder] = None,
     ) -> None:
         self.cfg = cfg
+        if cfg.output_format not in ("rgb", "i420"):
+            raise ValueError(
+                f"output_format must be 'rgb' or 'i420', got {cfg.output_format!r}")
+        if cfg.output_format == "i420" and (cfg.height % 2 or cfg.width % 2):
+            raise ValueError(
+                f"output_format='i420' needs even height and width, got "
+                f"{cfg.height}x{cfg.width}")
         self.device = torch.device(cfg.device if torch.cuda.is_available() or cfg.device == "cpu" else "cpu")
         self.dtype = getattr(torch, cfg.dtype) if self.device.type == "cuda" else torch.float32
         torch.manual_seed(cfg.seed)
@@ -253,6 +260,8 @@ class StreamDiffusionEngine:
             raise ValueError(f"fit_mode must be one of {ops.FIT_MODES}, got {cfg.fit_mode!r}")
         # last source (height, width) seen per slot — stats()["ingest"]
         self._src_size: list = [None] * fbs
+        # "rgb" / "i420" as last handed in per slot
+        self._src_format: list = [None] * fbs
         self._ts_batch = self._coeff["sub_timesteps_tensor"].to(dev)
         self._prev_out: Optional[torch.Tensor] = None
         self._graph = None
@@ -610,6 +619,10 @@ class StreamDiffusionEngine:
         decoded = self.vae.decode(latent)
         if self.safety_checker is not None:
             decoded = self.safety_checker.filter(decoded)
+        if self.cfg.output_format == "i420":
+            # same launch count: the u8 rounding and the colour conversion
+            # are one kernel
+            return ops.postprocess_to_i420(decoded)
         return ops.postprocess_to_u8(decoded)
 
     @torch.no_grad()
@@ -733,16 +746,60 @@ class StreamDiffusionEngine:
             for src in srcs:
                 src.record_stream(stream)
 
+    def _i420_to_rgb_sources(self, frame_u8):
+        """Replace every I420 source (ops/interface.py: a 2-D (3Hs/2, Ws)
+        frame, a (fbs, 3Hs/2, Ws) batch, or such entries of a list) by its
+        RGB conversion on the device: uploaded at 1.5 B/px and converted
+        with ops.i420_to_rgb_u8 on the caller's stream right after the
+        upload. What comes back is what __call__ has always taken, so
+        everything downstream (equal-size copy, fit, similarity filter, the
+        stream A/B chain) is untouched. Returns (frames, per-slot formats)."""
+        def convert(t):
+            return ops.i420_to_rgb_u8(t.to(self.device, non_blocking=True))
+
+        def check_2d(t):
+            if not ops.is_i420(t):
+                raise ValueError(
+                    f"2-D frames must be I420 (3H/2, W) uint8 with even H, W, "
+                    f"got {tuple(t.shape)} {t.dtype}")
+
+        if isinstance(frame_u8, (list, tuple)):
+            fmts = ["i420" if t.dim() == 2 else "rgb" for t in frame_u8]
+            if "i420" not in fmts:
+                return frame_u8, fmts
+            out = []
+            for t in frame_u8:
+                if t.dim() == 2:
+                    check_2d(t)
+                    t = convert(t)
+                out.append(t)
+            return out, fmts
+        if frame_u8.dim() == 2:
+            check_2d(frame_u8)
+            return convert(frame_u8), ["i420"]
+        if frame_u8.dim() == 3 and frame_u8.shape[-1] != 3:
+            if not ops.is_i420(frame_u8):
+                raise ValueError(
+                    f"3-D frames must be (H,W,3) RGB or an I420 batch "
+                    f"(fbs, 3H/2, W) uint8, got {tuple(frame_u8.shape)} {frame_u8.dtype}")
+            return convert(frame_u8), ["i420"] * frame_u8.shape[0]
+        n = 1 if frame_u8.dim() == 3 else frame_u8.shape[0]
+        return frame_u8, ["rgb"] * n
+
     @torch.no_grad()
     def __call__(self, frame_u8) -> torch.Tensor:
         """frame_u8: (H,W,3) or (fbs,H,W,3) uint8 RGB on any device, or a
         list/tuple of fbs (Hs,Ws,3) frames of differing sizes. Frames whose
         size is not the engine's (cfg.height, cfg.width) are uploaded at
-        source size and fitted on the device (cfg.fit_mode).
-        Returns stylised (H,W,3) / (fbs,H,W,3) uint8 RGB on self.device."""
+        source size and fitted on the device (cfg.fit_mode). Any source may
+        instead be an I420 frame ((3Hs/2,Ws), a (fbs,3Hs/2,Ws) batch, or
+        list entries of either format): it is converted on the device.
+        Returns stylised (H,W,3) / (fbs,H,W,3) uint8 RGB on self.device, or
+        (3H/2,W) / (fbs,3H/2,W) I420 with cfg.output_format == "i420"."""
         assert self._prepared, "call prepare() first"
         cfg = self.cfg
         eng_shape = (cfg.height, cfg.width, 3)
+        frame_u8, src_format = self._i420_to_rgb_sources(frame_u8)
         # srcs: per-slot source frames when any of them needs fitting;
         # None = everything is engine-sized (the path is what it always was)
         srcs = None
@@ -788,6 +845,7 @@ class StreamDiffusionEngine:
                     self._fit_into(srcs, frame_u8)
                     srcs = None
 
+        self._src_format = src_format
         if self.sim_filter is not None and self._prev_out is not None:
             # on-device pooled cosine (centering + 64x64 avg-pool inside
             # the filter); the only CPU sync is one scalar read that waits
@@ -860,6 +918,15 @@ class StreamDiffusionEngine:
                 for sz in getattr(self, "_src_size", [])
             ],
         }
+        fmts = getattr(self, "_src_format", [])
+        if self.cfg.output_format == "i420" or "i420" in fmts:
+            self._yuv_seen = True
+        if getattr(self, "_yuv_seen", False):
+            # "rgb" / "i420" as last handed in per slot (None: no frame
+            # yet). Reported once YUV is in play (I420 output configured or
+            # an I420 frame seen), so RGB-only deployments keep the ingest
+            # record they had
+            d["ingest"]["source_format"] = list(fmts)
         if self.cfg.use_fp8:
             d["fp8"] = {
                 "active": self.fp8_active,

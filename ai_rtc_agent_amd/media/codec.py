@@ -28,7 +28,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ..config import EncoderConfig, hw_decode_enabled, hw_encode_enabled
+from ..config import EncoderConfig, hw_decode_enabled, hw_encode_enabled, media_yuv
 
 _MAGIC_I = b"RZI1"
 _MAGIC_P = b"RZP1"
@@ -36,6 +36,17 @@ _MAGIC_P = b"RZP1"
 
 class CodecUnavailable(RuntimeError):
     pass
+
+
+def _rgb_frame(frame_u8: torch.Tensor) -> torch.Tensor:
+    """Codecs without plane input take RGB: an I420 frame (ops/interface.py)
+    is converted on the CPU reference path first, so no codec ever fails on
+    one (VideoStreamTrack passes warm-up frames through untouched)."""
+    from .. import ops
+
+    if ops.is_i420(frame_u8):
+        return ops.i420_to_rgb_u8(frame_u8.detach().to("cpu").contiguous())
+    return frame_u8
 
 
 class VcnH264Codec:
@@ -130,7 +141,7 @@ class VcnH264Codec:
         ext = ops.hip_ext()
         if ext is None or not hasattr(ext, "VcnEncoder"):
             raise CodecUnavailable("native extension without VcnEncoder")
-        arr = frame_u8.detach().to("cpu", torch.uint8).contiguous()
+        arr = _rgb_frame(frame_u8).detach().to("cpu", torch.uint8).contiguous()
         h, w = int(arr.shape[0]), int(arr.shape[1])
         if self._enc_dims != (w, h):
             self._enc = ext.VcnEncoder(w, h)  # raises on session failure
@@ -167,7 +178,11 @@ class H264SwCodec:
     FPS_ASSUMED = 30
 
     def __init__(self, cfg: EncoderConfig | None = None,
-                 keyframe_interval: int = 60):
+                 keyframe_interval: int = 60, yuv: bool = False):
+        # yuv: decode() hands out I420 frames (the decoder's own planes, no
+        # colour conversion) instead of RGB; encode() takes either format
+        # whatever this says
+        self.yuv = yuv
         try:
             from .. import ops
 
@@ -190,8 +205,16 @@ class H264SwCodec:
         return max(2048, bps // 8 // self.FPS_ASSUMED)
 
     def encode(self, frame_u8: torch.Tensor, keyframe: bool = False) -> bytes:
+        from .. import ops
+
+        # an I420 frame (1.5 B/px off the device) goes to the encoder's
+        # plane input: no colour conversion on this side at all
+        yuv = ops.is_i420(frame_u8) and frame_u8.dim() == 2
         arr = frame_u8.detach().to("cpu", torch.uint8).contiguous()
-        h, w = int(arr.shape[0]), int(arr.shape[1])
+        if yuv:
+            h, w = ops.i420_size(arr)
+        else:
+            h, w = int(arr.shape[0]), int(arr.shape[1])
         if self._enc_dims != (w, h):
             # mb_mode=2: per-MB I_16x16 / I_4x4 decision (I_4x4 with full
             # mode search wins on moderately detailed macroblocks).
@@ -208,8 +231,8 @@ class H264SwCodec:
         # PLI sets keyframe=True through the transport (media/rtc.py)
         force = keyframe or self._enc_count % self.keyframe_interval == 0
         self._enc_count += 1
-        data = self._enc.encode(arr.numpy().tobytes(), self._qp,
-                                keyframe=bool(force))
+        enc = self._enc.encode_yuv if yuv else self._enc.encode
+        data = enc(arr.numpy().tobytes(), self._qp, keyframe=bool(force))
         # QP rate control toward the per-frame byte budget. P frames are
         # motion-dependent and usually far under budget, so only keyframes
         # drive the QP down; either frame type can push it up.
@@ -221,10 +244,20 @@ class H264SwCodec:
         return data
 
     def decode(self, data: bytes) -> Optional[torch.Tensor]:
-        r = self._dec.decode(bytes(data))
-        if r is None:
-            return None
-        buf, w, h = r
+        if self.yuv:
+            r = self._dec.decode_yuv(bytes(data))
+            if r is None:
+                return None
+            buf, w, h, is_i420 = r
+            if is_i420:
+                return torch.frombuffer(
+                    bytearray(buf), dtype=torch.uint8).reshape(h * 3 // 2, w)
+            # odd (SPS-cropped) sizes cannot be I420: RGB as ever
+        else:
+            r = self._dec.decode(bytes(data))
+            if r is None:
+                return None
+            buf, w, h = r
         return torch.frombuffer(bytearray(buf), dtype=torch.uint8).reshape(h, w, 3)
 
 
@@ -258,7 +291,7 @@ class SoftwareCodec:
         return max(1024, bps // 8 // self.FPS_ASSUMED)
 
     def encode(self, frame_u8: torch.Tensor, keyframe: bool = False) -> bytes:
-        arr = frame_u8.detach().cpu().numpy().astype(np.uint8)
+        arr = _rgb_frame(frame_u8).detach().cpu().numpy().astype(np.uint8)
         h, w, _ = arr.shape
         force_key = keyframe or self._enc_prev is None or self._enc_count % self.keyframe_interval == 0
         self._enc_count += 1
@@ -330,6 +363,6 @@ def select_codec(cfg: EncoderConfig | None = None, role: str = "encode"):
         except CodecUnavailable:
             pass
     try:
-        return H264SwCodec(cfg=cfg or EncoderConfig())
+        return H264SwCodec(cfg=cfg or EncoderConfig(), yuv=media_yuv())
     except CodecUnavailable:
         return SoftwareCodec(cfg=cfg or EncoderConfig())

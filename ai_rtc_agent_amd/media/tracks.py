@@ -24,9 +24,16 @@ from .. import config
 
 @dataclass
 class VideoFrame:
-    """A video frame: u8 RGB tensor + timing metadata."""
+    """A video frame: u8 tensor + timing metadata.
 
-    tensor: torch.Tensor  # (H, W, 3) u8
+    The tensor is packed RGB (H, W, 3) or, with AIRTC_MEDIA_YUV, an I420
+    frame: 2-D contiguous (3*H/2, W) u8, H and W even, holding the tight
+    H*W Y plane, then (H/2)*(W/2) bytes of Cb, then as many of Cr (BT.601
+    limited range, the H.264 codec's own planes). The dimensionality tells
+    the two apart; ops.is_i420 / ops.i420_size / ops.i420_to_rgb_u8 read
+    one. Codecs and the engine accept both."""
+
+    tensor: torch.Tensor  # (H, W, 3) u8 RGB or (3H/2, W) u8 I420
     pts: int = 0
     time_base: float = 1.0 / 90000
 

@@ -326,6 +326,73 @@ void fit_resize_u8(torch::Tensor src, torch::Tensor dst, int64_t slot,
                       (int)ox, (int)oh, (int)ow, cur_stream());
 }
 
+// --- I420 colour conversion (color.hip) --------------------------------
+// shared validation: packed side `rgb` (B,H,W,3) of dtype rgb_dt, planar
+// side (B,3H/2,W) u8; `out` is the caller's tensor or a fresh one
+void check_rgb_side(const torch::Tensor& rgb, c10::ScalarType rgb_dt,
+                    const char* what) {
+  TORCH_CHECK(rgb.dtype() == rgb_dt, what, ": wrong dtype");
+  TORCH_CHECK(rgb.dim() == 4 && rgb.size(3) == 3, what,
+              " must be (B, H, W, 3)");
+  const int64_t B = rgb.size(0), H = rgb.size(1), W = rgb.size(2);
+  TORCH_CHECK(B >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0,
+              "I420 needs even H, W >= 2, got ", H, "x", W);
+  TORCH_CHECK(H * W * 3 < (1LL << 31) && B < (1LL << 31), "frame too large");
+}
+
+torch::Tensor i420_out(const torch::Tensor& like,
+                       const c10::optional<torch::Tensor>& out,
+                       at::IntArrayRef sizes) {
+  if (!out.has_value())
+    return torch::empty(sizes, like.options().dtype(torch::kUInt8));
+  CHECK_IN((*out));
+  TORCH_CHECK(out->dtype() == torch::kUInt8, "out must be uint8");
+  TORCH_CHECK(out->device() == like.device(), "out on a different device");
+  TORCH_CHECK(out->sizes() == sizes, "out has the wrong shape");
+  return *out;
+}
+
+torch::Tensor to_i420(torch::Tensor x, c10::optional<torch::Tensor> out,
+                      bool f16) {
+  CHECK_IN(x);
+  check_rgb_side(x, f16 ? torch::kHalf : torch::kByte, "x");
+  const int64_t B = x.size(0), H = x.size(1), W = x.size(2);
+  auto o = i420_out(x, out, {B, H / 2 * 3, W});
+  if (f16)
+    airtc_postprocess_i420(h_ptr(x), o.data_ptr<uint8_t>(), (int)B, (int)H,
+                           (int)W, cur_stream());
+  else
+    airtc_rgb_u8_to_i420(x.data_ptr<uint8_t>(), o.data_ptr<uint8_t>(), (int)B,
+                         (int)H, (int)W, cur_stream());
+  return o;
+}
+
+torch::Tensor rgb_u8_to_i420(torch::Tensor x,
+                             c10::optional<torch::Tensor> out) {
+  return to_i420(x, out, false);
+}
+
+torch::Tensor postprocess_i420(torch::Tensor img,
+                               c10::optional<torch::Tensor> out) {
+  return to_i420(img, out, true);
+}
+
+torch::Tensor i420_to_rgb_u8(torch::Tensor x,
+                             c10::optional<torch::Tensor> out) {
+  CHECK_IN(x);
+  TORCH_CHECK(x.dtype() == torch::kUInt8, "x: wrong dtype");
+  TORCH_CHECK(x.dim() == 3, "x must be (B, 3H/2, W)");
+  const int64_t B = x.size(0), R = x.size(1), W = x.size(2);
+  TORCH_CHECK(B >= 1 && R >= 3 && R % 3 == 0 && W >= 2 && W % 2 == 0,
+              "I420 needs (B, 3H/2, W) with even H, W >= 2, got ", R, "x", W);
+  const int64_t H = R / 3 * 2;
+  TORCH_CHECK(H * W * 3 < (1LL << 31) && B < (1LL << 31), "frame too large");
+  auto o = i420_out(x, out, {B, H, W, 3});
+  airtc_i420_to_rgb_u8(x.data_ptr<uint8_t>(), o.data_ptr<uint8_t>(), (int)B,
+                       (int)H, (int)W, cur_stream());
+  return o;
+}
+
 // --- software H.264 baseline-intra codec (h264sw.cpp) -----------------
 extern "C" {
 void* airtc_h264enc_create(int w, int h);
@@ -334,12 +401,16 @@ void airtc_h264enc_destroy(void*);
 int airtc_h264enc_encode(void*, const uint8_t*, int qp, uint8_t*, int cap);
 int airtc_h264enc_encode_ex(void*, const uint8_t*, int qp, int force_idr,
                             uint8_t*, int cap);
+int airtc_h264enc_encode_yuv(void*, const uint8_t*, int qp, int force_idr,
+                             uint8_t*, int cap);
 void airtc_h264enc_set_mb_mode(void*, int m);
 void airtc_h264_pred4(int, const uint8_t*, const uint8_t*, uint8_t, int, int,
                       int, uint8_t*);
 void* airtc_h264dec_create();
 void airtc_h264dec_destroy(void*);
 int airtc_h264dec_decode(void*, const uint8_t*, int, uint8_t*, int, int*, int*);
+int airtc_h264dec_decode_yuv(void*, const uint8_t*, int, uint8_t*, int, int*,
+                             int*, int*);
 void airtc_h264dec_dims(void*, int*, int*);
 int airtc_h264sw_table_check();
 }
@@ -362,19 +433,33 @@ class H264SwEncoder {
   pybind11::bytes encode(pybind11::bytes rgb, int qp, bool keyframe = true) {
     std::string s(rgb);
     TORCH_CHECK((int)s.size() == w_ * h_ * 3, "rgb buffer size mismatch");
+    return run(s, qp, keyframe, /*yuv=*/false);
+  }
+  // same encode from tight I420 planes (w*h Y, then Cb, then Cr): the
+  // colour conversion already happened, e.g. on the GPU
+  pybind11::bytes encode_yuv(pybind11::bytes i420, int qp,
+                             bool keyframe = true) {
+    std::string s(i420);
+    TORCH_CHECK(w_ % 2 == 0 && h_ % 2 == 0, "I420 needs even dimensions");
+    TORCH_CHECK((int)s.size() == w_ * h_ * 3 / 2,
+                "i420 buffer size mismatch");
+    return run(s, qp, keyframe, /*yuv=*/true);
+  }
+
+ private:
+  pybind11::bytes run(const std::string& s, int qp, bool keyframe, bool yuv) {
     std::vector<uint8_t> out((size_t)w_ * h_ * 6 + 4096);
     int n;
     {
       pybind11::gil_scoped_release nogil;
-      n = airtc_h264enc_encode_ex(handle_, (const uint8_t*)s.data(), qp,
-                                  keyframe ? 1 : 0, out.data(),
-                                  (int)out.size());
+      n = (yuv ? airtc_h264enc_encode_yuv : airtc_h264enc_encode_ex)(
+          handle_, (const uint8_t*)s.data(), qp, keyframe ? 1 : 0, out.data(),
+          (int)out.size());
     }
     TORCH_CHECK(n > 0, "h264 encode failed rc=", n);
     return pybind11::bytes((const char*)out.data(), n);
   }
 
- private:
   void* handle_;
   int w_, h_;
 };
@@ -389,29 +474,47 @@ class H264SwDecoder {
   // returns (rgb_bytes, w, h) or None (no frame in this AU / undecodable)
   pybind11::object decode(pybind11::bytes data) {
     std::string s(data);
-    int w = 0, h = 0, rc;
-    {
-      pybind11::gil_scoped_release nogil;
-      rc = airtc_h264dec_decode(handle_, (const uint8_t*)s.data(),
-                                (int)s.size(), buf_.data(), (int)buf_.size(),
-                                &w, &h);
-      if (rc == -8) {  // output buffer too small: size from the parsed SPS
-        int dw = 0, dh = 0;
-        airtc_h264dec_dims(handle_, &dw, &dh);
-        if (dw > 0 && dh > 0) {
-          buf_.resize((size_t)dw * dh * 3);
-          rc = airtc_h264dec_decode(handle_, (const uint8_t*)s.data(),
-                                    (int)s.size(), buf_.data(),
-                                    (int)buf_.size(), &w, &h);
-        }
-      }
-    }
-    if (rc != 1) return pybind11::none();
+    int w = 0, h = 0, is_yuv = 0;
+    if (run(s, /*yuv=*/false, &w, &h, &is_yuv) != 1) return pybind11::none();
     return pybind11::make_tuple(
         pybind11::bytes((const char*)buf_.data(), (size_t)w * h * 3), w, h);
   }
+  // same decode, picture handed out as tight I420 planes (no colour
+  // conversion): (bytes, w, h, is_i420) or None. is_i420 is False, and the
+  // bytes are RGB24 as from decode(), when w or h is odd
+  pybind11::object decode_yuv(pybind11::bytes data) {
+    std::string s(data);
+    int w = 0, h = 0, is_yuv = 0;
+    if (run(s, /*yuv=*/true, &w, &h, &is_yuv) != 1) return pybind11::none();
+    const size_t n = is_yuv ? (size_t)w * h * 3 / 2 : (size_t)w * h * 3;
+    return pybind11::make_tuple(pybind11::bytes((const char*)buf_.data(), n),
+                                w, h, is_yuv != 0);
+  }
 
  private:
+  int call(const std::string& s, bool yuv, int* w, int* h, int* is_yuv) {
+    if (yuv)
+      return airtc_h264dec_decode_yuv(handle_, (const uint8_t*)s.data(),
+                                      (int)s.size(), buf_.data(),
+                                      (int)buf_.size(), w, h, is_yuv);
+    return airtc_h264dec_decode(handle_, (const uint8_t*)s.data(),
+                                (int)s.size(), buf_.data(), (int)buf_.size(),
+                                w, h);
+  }
+  int run(const std::string& s, bool yuv, int* w, int* h, int* is_yuv) {
+    pybind11::gil_scoped_release nogil;
+    int rc = call(s, yuv, w, h, is_yuv);
+    if (rc == -8) {  // output buffer too small: size from the parsed SPS
+      int dw = 0, dh = 0;
+      airtc_h264dec_dims(handle_, &dw, &dh);
+      if (dw > 0 && dh > 0) {
+        buf_.resize((size_t)dw * dh * 3);
+        rc = call(s, yuv, w, h, is_yuv);
+      }
+    }
+    return rc;
+  }
+
   void* handle_;
   std::vector<uint8_t> buf_ = std::vector<uint8_t>((size_t)1024 * 1024 * 3);
 };
@@ -680,6 +783,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("postprocess_u8", &postprocess_u8);
   m.def("fit_resize_u8", &fit_resize_u8,
         "crop + antialiased resize of a u8 RGB frame into one slot");
+  m.def("rgb_u8_to_i420", &rgb_u8_to_i420,
+        "(B,H,W,3) u8 RGB -> (B,3H/2,W) u8 I420 (BT.601 limited, integer)",
+        pybind11::arg("x"), pybind11::arg("out") = pybind11::none());
+  m.def("postprocess_i420", &postprocess_i420,
+        "(B,H,W,3) f16 in [-1,1] -> (B,3H/2,W) u8 I420 in one kernel",
+        pybind11::arg("img"), pybind11::arg("out") = pybind11::none());
+  m.def("i420_to_rgb_u8", &i420_to_rgb_u8,
+        "(B,3H/2,W) u8 I420 -> (B,H,W,3) u8 RGB",
+        pybind11::arg("x"), pybind11::arg("out") = pybind11::none());
   m.def("conv2d_fp8", &conv2d_fp8,
         "fp8 e4m3 implicit-GEMM conv2d on the MX-scaled MFMA (NHWC)",
         pybind11::arg("x"), pybind11::arg("w_fp8"), pybind11::arg("dq"),
@@ -704,7 +816,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            pybind11::arg("mb_mode") = 0)
       .def("encode", &H264SwEncoder::encode, pybind11::arg("rgb"),
            pybind11::arg("qp"), pybind11::arg("keyframe") = true,
-           "RGB24 bytes + QP -> Annex-B (IDR, or P when keyframe=false)");
+           "RGB24 bytes + QP -> Annex-B (IDR, or P when keyframe=false)")
+      .def("encode_yuv", &H264SwEncoder::encode_yuv, pybind11::arg("i420"),
+           pybind11::arg("qp"), pybind11::arg("keyframe") = true,
+           "tight I420 bytes + QP -> Annex-B, no colour conversion");
   m.def("h264_pred4",
         [](int mode, pybind11::bytes top, pybind11::bytes left, int tl,
            bool ht, bool hl, bool htl) {
@@ -720,7 +835,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   pybind11::class_<H264SwDecoder>(m, "H264SwDecoder")
       .def(pybind11::init<>())
       .def("decode", &H264SwDecoder::decode,
-           "Annex-B AU -> (rgb bytes, w, h) | None");
+           "Annex-B AU -> (rgb bytes, w, h) | None")
+      .def("decode_yuv", &H264SwDecoder::decode_yuv,
+           "Annex-B AU -> (i420 bytes, w, h, is_i420) | None");
   pybind11::class_<VcnEncoder>(m, "VcnEncoder")
       .def(pybind11::init<int, int>())
       .def("encode", &VcnEncoder::encode,

@@ -493,9 +493,45 @@ static void rgb_to_yuv420_rows(const uint8_t* rgb, int w, int h, int pw,
   }
 }
 
-static void rgb_to_yuv420(const uint8_t* rgb, int w, int h, int pw, int ph,
-                          uint8_t* Y, uint8_t* Cb, uint8_t* Cr) {
-  rgb_to_yuv420_rows(rgb, w, h, pw, 0, ph, Y, Cb, Cr);
+// tight I420 planes (w*h Y, then (w/2)*(h/2) Cb, then Cr; w, h even) into
+// the padded planes, luma rows [y0, y1): the counterpart of
+// rgb_to_yuv420_rows for frames that arrive already converted. Right and
+// bottom padding replicates the edge sample of each plane.
+static void i420_to_planes_rows(const uint8_t* i420, int w, int h, int pw,
+                                int y0, int y1, uint8_t* Y, uint8_t* Cb,
+                                uint8_t* Cr) {
+  for (int y = y0; y < y1; ++y) {
+    const uint8_t* row = i420 + (size_t)std::min(y, h - 1) * w;
+    uint8_t* yo = &Y[(size_t)y * pw];
+    memcpy(yo, row, (size_t)w);
+    memset(yo + w, row[w - 1], (size_t)(pw - w));
+  }
+  const int cw = pw / 2, cwi = w / 2, chi = h / 2;
+  const uint8_t* src[2] = {i420 + (size_t)w * h,
+                           i420 + (size_t)w * h + (size_t)cwi * chi};
+  uint8_t* dst[2] = {Cb, Cr};
+  for (int comp = 0; comp < 2; ++comp)
+    for (int y = y0 / 2; y < y1 / 2; ++y) {
+      const uint8_t* row = src[comp] + (size_t)std::min(y, chi - 1) * cwi;
+      uint8_t* co = &dst[comp][(size_t)y * cw];
+      memcpy(co, row, (size_t)cwi);
+      memset(co + cwi, row[cwi - 1], (size_t)(cw - cwi));
+    }
+}
+
+// visible w x h window of padded planes -> tight I420 (w, h even)
+static void planes_to_i420(const uint8_t* Y, const uint8_t* Cb,
+                           const uint8_t* Cr, int pw, int w, int h,
+                           uint8_t* i420) {
+  for (int y = 0; y < h; ++y)
+    memcpy(i420 + (size_t)y * w, Y + (size_t)y * pw, (size_t)w);
+  const int cw = pw / 2, cwi = w / 2, chi = h / 2;
+  uint8_t* ob = i420 + (size_t)w * h;
+  uint8_t* orr = ob + (size_t)cwi * chi;
+  for (int y = 0; y < chi; ++y) {
+    memcpy(ob + (size_t)y * cwi, Cb + (size_t)y * cw, (size_t)cwi);
+    memcpy(orr + (size_t)y * cwi, Cr + (size_t)y * cw, (size_t)cwi);
+  }
 }
 
 static void yuv420_to_rgb(const uint8_t* Y, const uint8_t* Cb, const uint8_t* Cr,
@@ -1549,6 +1585,30 @@ struct Encoder {
   // exists yet.
   int encode_ex(const uint8_t* rgb, int qp, int force_idr, uint8_t* out,
                 int cap) {
+    return encode_frame(rgb, /*yuv=*/false, qp, force_idr, out, cap);
+  }
+
+  // Same encode from tight I420 planes (w*h Y, (w/2)*(h/2) Cb, then Cr):
+  // the planes are copied where encode_ex converts, everything after plane
+  // preparation is shared. Needs even w, h.
+  int encode_yuv_ex(const uint8_t* i420, int qp, int force_idr, uint8_t* out,
+                    int cap) {
+    if ((w | h) & 1) return -3;
+    return encode_frame(i420, /*yuv=*/true, qp, force_idr, out, cap);
+  }
+
+  // fill the padded source planes, luma rows [y0, y1) (16-aligned)
+  void prepare_rows(const uint8_t* src, bool yuv, int y0, int y1) {
+    if (yuv)
+      i420_to_planes_rows(src, w, h, pw, y0, y1, Y.data(), Cb.data(),
+                          Cr.data());
+    else
+      rgb_to_yuv420_rows(src, w, h, pw, y0, y1, Y.data(), Cb.data(),
+                         Cr.data());
+  }
+
+  int encode_frame(const uint8_t* src, bool yuv, int qp, int force_idr,
+                   uint8_t* out, int cap) {
     if (qp < 10) qp = 10;
     if (qp > 48) qp = 48;
     const bool idr = force_idr || !have_ref;
@@ -1557,8 +1617,7 @@ struct Encoder {
     // per frame instead of two, and the band stays L2-hot into its encode;
     // encode never reads outside its own band: intra prediction does not
     // cross slice boundaries). Single-slice path converts here.
-    if (ns == 1)
-      rgb_to_yuv420(rgb, w, h, pw, ph, Y.data(), Cb.data(), Cr.data());
+    if (ns == 1) prepare_rows(src, yuv, 0, ph);
     nnz.reset(mbw, mbh);
     enc_i4modes.assign((size_t)mbw * mbh * 16, -1);
 
@@ -1583,8 +1642,7 @@ struct Encoder {
       const int r0 = si * band, r1 = std::min(mbh, r0 + band);
       if (r0 >= r1) return;
       if (ns > 1)  // fused per-band colour conversion (16 | band rows)
-        rgb_to_yuv420_rows(rgb, w, h, pw, r0 * 16, std::min(ph, r1 * 16),
-                           Y.data(), Cb.data(), Cr.data());
+        prepare_rows(src, yuv, r0 * 16, std::min(ph, r1 * 16));
       const int slice_start = r0 * mbw;
       BitWriter wtr;
       wtr.ue((uint32_t)slice_start);  // first_mb_in_slice
@@ -2003,6 +2061,22 @@ struct Decoder {
 
   int decode_au(const uint8_t* data, int len, uint8_t* rgb, int cap, int* ow,
                 int* oh) {
+    int is_yuv;
+    return decode_au_out(data, len, rgb, cap, ow, oh, false, &is_yuv);
+  }
+
+  // decode_au that hands the picture out as tight I420 planes (the visible
+  // w x h window of the reconstruction, no colour conversion) and sets
+  // *is_yuv = 1. Cropped streams with an odd w or h cannot be I420: they
+  // come out as RGB exactly as from decode_au, *is_yuv = 0. Decoder state
+  // advances identically either way, so a stream may mix the two calls.
+  int decode_au_yuv(const uint8_t* data, int len, uint8_t* out, int cap,
+                    int* ow, int* oh, int* is_yuv) {
+    return decode_au_out(data, len, out, cap, ow, oh, true, is_yuv);
+  }
+
+  int decode_au_out(const uint8_t* data, int len, uint8_t* out, int cap,
+                    int* ow, int* oh, bool want_yuv, int* is_yuv) {
     auto nals = h264::split_annexb(data, (size_t)len);
     bool got_frame = false;
     std::vector<SliceJob> slices;
@@ -2112,8 +2186,14 @@ struct Decoder {
     }
     if (!got_frame) return 0;
     const int w = sps.w(), h = sps.h();
-    if (cap < w * h * 3) return -8;
-    yuv420_to_rgb(rY.data(), rCb.data(), rCr.data(), sps.pw, w, h, rgb);
+    *is_yuv = want_yuv && !((w | h) & 1);
+    if (*is_yuv) {
+      if (cap < w * h * 3 / 2) return -8;
+      planes_to_i420(rY.data(), rCb.data(), rCr.data(), sps.pw, w, h, out);
+    } else {
+      if (cap < w * h * 3) return -8;
+      yuv420_to_rgb(rY.data(), rCb.data(), rCr.data(), sps.pw, w, h, out);
+    }
     *ow = w;
     *oh = h;
     return 1;
@@ -2127,8 +2207,10 @@ struct Decoder {
 // ---------------------------------------------------------------------------
 extern "C" {
 
+// pictures smaller than a macroblock are padded to one and SPS-cropped like
+// any other size that is no multiple of 16
 void* airtc_h264enc_create(int w, int h) {
-  if (w < 16 || h < 16 || w > 8192 || h > 8192) return nullptr;
+  if (w < 2 || h < 2 || w > 8192 || h > 8192) return nullptr;
   return new h264sw::Encoder(w, h);
 }
 // number of slices (MB-row bands) encoded in parallel threads
@@ -2151,6 +2233,12 @@ int airtc_h264enc_encode_ex(void* h, const uint8_t* rgb, int qp,
   return ((h264sw::Encoder*)h)->encode_ex(rgb, qp, force_idr, out, cap);
 }
 
+// encode from tight I420 planes (w*h*3/2 bytes; even w, h)
+int airtc_h264enc_encode_yuv(void* h, const uint8_t* i420, int qp,
+                             int force_idr, uint8_t* out, int cap) {
+  return ((h264sw::Encoder*)h)->encode_yuv_ex(i420, qp, force_idr, out, cap);
+}
+
 void* airtc_h264dec_create() { return new h264sw::Decoder(); }
 void airtc_h264dec_destroy(void* h) { delete (h264sw::Decoder*)h; }
 // display dims from the last parsed SPS (0 until one arrives)
@@ -2162,6 +2250,14 @@ void airtc_h264dec_dims(void* h, int* w, int* out_h) {
 int airtc_h264dec_decode(void* h, const uint8_t* data, int len, uint8_t* rgb,
                          int cap, int* w, int* out_h) {
   return ((h264sw::Decoder*)h)->decode_au(data, len, rgb, cap, w, out_h);
+}
+
+// decode to tight I420 (*is_yuv = 1), or to RGB for odd dims (*is_yuv = 0)
+int airtc_h264dec_decode_yuv(void* h, const uint8_t* data, int len,
+                             uint8_t* out, int cap, int* w, int* out_h,
+                             int* is_yuv) {
+  return ((h264sw::Decoder*)h)->decode_au_yuv(data, len, out, cap, w, out_h,
+                                              is_yuv);
 }
 
 // test hook: run one 4x4 intra prediction (decoder path) for golden checks

@@ -25,6 +25,20 @@ void airtc_upsample2x_f16(const uint16_t* in, uint16_t* out, int B, int H,
 void airtc_fit_resize_u8(const uint8_t* src, int Ws, uint8_t* dst, int H,
                          int W, int y0, int x0, int ch, int cw, int oy,
                          int ox, int oh, int ow, hipStream_t s);
+// colour (color.hip) --------------------------------------------------------
+// I420 frame = (3H/2, W) u8: H*W of Y, then (H/2)*(W/2) of Cb, then of Cr,
+// tight; BT.601 limited range in the software codec's integer arithmetic.
+// H and W even and >= 2 (validated by the caller, ext.cpp); batches are B
+// tight frames.
+// (B,H,W,3) u8 RGB -> (B,3H/2,W) I420
+void airtc_rgb_u8_to_i420(const uint8_t* in, uint8_t* out, int B, int H,
+                          int W, hipStream_t s);
+// (B,H,W,3) f16 in [-1,1] -> I420: postprocess_u8 fused with the above
+void airtc_postprocess_i420(const uint16_t* in, uint8_t* out, int B, int H,
+                            int W, hipStream_t s);
+// (B,3H/2,W) I420 -> (B,H,W,3) u8 RGB, chroma nearest-replicated
+void airtc_i420_to_rgb_u8(const uint8_t* in, uint8_t* out, int B, int H,
+                          int W, hipStream_t s);
 // fused LCM scheduler math (one kernel each; coefficients are per-batch-row
 // f32 arrays of B entries, per_b = elements per batch row)
 void airtc_sched_add_noise(const uint16_t* x0, const uint16_t* noise,

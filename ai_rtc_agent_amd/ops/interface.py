@@ -686,3 +686,200 @@ def postprocess_to_u8(img: torch.Tensor) -> torch.Tensor:
         return _require_ext().postprocess_u8(img.contiguous())
     x = (img.float() + 1.0) * 127.5
     return x.round().clamp(0, 255).to(torch.uint8)
+
+
+# ---------------------------------------------------------------------------
+# YUV 4:2:0 frames (ops/csrc/color.hip)
+# ---------------------------------------------------------------------------
+# The frame format, stated once for the whole package:
+#
+# An I420 frame is a 2-D contiguous uint8 tensor of shape (3*H/2, W), H and W
+# even: the first H*W bytes are the Y plane, the next (H/2)*(W/2) bytes Cb,
+# the last (H/2)*(W/2) bytes Cr. All three planes are tight; the chroma
+# planes are flat bytes inside the (H/2, W) tail (H need not be a multiple of
+# 4). A batch is (B, 3*H/2, W). The dimensionality tells the formats apart:
+# (H, W, 3) / (B, H, W, 3) is packed RGB, (3H/2, W) / (B, 3H/2, W) is I420
+# (W is even, so a trailing dimension of 3 is always RGB).
+#
+# The arithmetic is the software codec's (ops/csrc/h264sw.cpp), BT.601
+# limited range in integers, so every conversion below is bit-exact between
+# the HIP kernels, the torch reference and the codec:
+#   Y  = clip8(((66R + 129G + 25B + 128) >> 8) + 16)             per pixel
+#   R' = (a+b+c+d+2) >> 2 per channel over each 2x2 block, then
+#   Cb = clip8(((-38R' - 74G' + 112B' + 128) >> 8) + 128)
+#   Cr = clip8(((112R' - 94G' - 18B' + 128) >> 8) + 128)
+# and back, chroma nearest-replicated (Cb[y/2][x/2]), C=Y-16, D=Cb-128,
+# E=Cr-128:
+#   R = clip8((298C + 409E + 128) >> 8)
+#   G = clip8((298C - 100D - 208E + 128) >> 8)
+#   B = clip8((298C + 516D + 128) >> 8)
+# (>> is an arithmetic shift: floor division by 256).
+
+def is_i420(t: torch.Tensor) -> bool:
+    """True when `t` has the shape and dtype of an I420 frame or batch."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        return False
+    if t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[-1] == 3):
+        return False
+    rows, w = int(t.shape[-2]), int(t.shape[-1])
+    return rows >= 3 and rows % 3 == 0 and w >= 2 and w % 2 == 0
+
+
+def i420_size(t: torch.Tensor) -> tuple:
+    """(H, W) of the picture an I420 frame or batch holds."""
+    _check_i420(t)
+    return int(t.shape[-2]) // 3 * 2, int(t.shape[-1])
+
+
+def _check_i420(t: torch.Tensor) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        raise ValueError(
+            f"I420 frames are uint8 tensors, got {getattr(t, 'dtype', type(t))}")
+    if t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[-1] == 3):
+        raise ValueError(
+            f"I420 frames are (3H/2, W) or (B, 3H/2, W), got {tuple(t.shape)}")
+    if not is_i420(t):
+        raise ValueError(
+            f"I420 needs even H, W >= 2 in (3H/2, W), got {tuple(t.shape)}")
+
+
+def _check_rgb_for_i420(x: torch.Tensor, dtype: torch.dtype | None) -> None:
+    if dtype is not None and x.dtype != dtype:
+        raise ValueError(f"expected {dtype}, got {x.dtype}")
+    if dtype is None and not x.dtype.is_floating_point:
+        raise ValueError(f"expected a floating-point image, got {x.dtype}")
+    if x.dim() not in (3, 4) or x.shape[-1] != 3:
+        raise ValueError(
+            f"expected (H,W,3) or (B,H,W,3), got {tuple(x.shape)}")
+    h, w = int(x.shape[-3]), int(x.shape[-2])
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise ValueError(f"I420 needs even H, W >= 2, got {h}x{w}")
+
+
+def _on_kernel(x: torch.Tensor) -> bool:
+    return x.is_cuda and os.environ.get("AIRTC_FORCE_EAGER") != "1"
+
+
+def _clip8(v: torch.Tensor) -> torch.Tensor:
+    return v.clamp(0, 255).to(torch.uint8)
+
+
+def _rgb_u8_to_i420_ref(x: torch.Tensor) -> torch.Tensor:
+    """(B,H,W,3) u8 -> (B,3H/2,W) u8 with the integer formulas above."""
+    b, h, w, _ = x.shape
+    p = x.to(torch.int32)
+    r, g, bl = p[..., 0], p[..., 1], p[..., 2]
+    y = _clip8(torch.bitwise_right_shift(66 * r + 129 * g + 25 * bl + 128, 8) + 16)
+    q = p.reshape(b, h // 2, 2, w // 2, 2, 3).sum(dim=(2, 4))
+    q = torch.bitwise_right_shift(q + 2, 2)
+    r, g, bl = q[..., 0], q[..., 1], q[..., 2]
+    cb = _clip8(torch.bitwise_right_shift(-38 * r - 74 * g + 112 * bl + 128, 8) + 128)
+    cr = _clip8(torch.bitwise_right_shift(112 * r - 94 * g - 18 * bl + 128, 8) + 128)
+    out = torch.cat([y.reshape(b, -1), cb.reshape(b, -1), cr.reshape(b, -1)], dim=1)
+    return out.reshape(b, h // 2 * 3, w).contiguous()
+
+
+def _i420_to_rgb_u8_ref(x: torch.Tensor) -> torch.Tensor:
+    """(B,3H/2,W) u8 -> (B,H,W,3) u8 with the integer formulas above."""
+    b, rows, w = x.shape
+    h = rows // 3 * 2
+    flat = x.reshape(b, -1).to(torch.int32)
+    n, nc = h * w, (h // 2) * (w // 2)
+    c = flat[:, :n].reshape(b, h, w) - 16
+
+    def up(plane):
+        plane = plane.reshape(b, h // 2, w // 2) - 128
+        return plane.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
+
+    d, e = up(flat[:, n:n + nc]), up(flat[:, n + nc:])
+    sh = torch.bitwise_right_shift
+    r = _clip8(sh(298 * c + 409 * e + 128, 8))
+    g = _clip8(sh(298 * c - 100 * d - 208 * e + 128, 8))
+    bl = _clip8(sh(298 * c + 516 * d + 128, 8))
+    return torch.stack([r, g, bl], dim=-1).contiguous()
+
+
+def _batched(x: torch.Tensor, dims: int):
+    """(x with a leading batch dim, whether one was added)."""
+    return (x.unsqueeze(0), True) if x.dim() == dims else (x, False)
+
+
+def _finish(res: torch.Tensor, out, squeeze: bool) -> torch.Tensor:
+    if out is not None:
+        return out
+    return res[0] if squeeze else res
+
+
+def _check_out(out, like: torch.Tensor, shape) -> None:
+    if out is None:
+        return
+    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) \
+            or out.device != like.device or not out.is_contiguous():
+        raise ValueError(
+            f"out must be a contiguous uint8 {tuple(shape)} tensor on "
+            f"{like.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+
+
+def rgb_u8_to_i420(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """u8 RGB (H,W,3) / (B,H,W,3) -> I420 (3H/2,W) / (B,3H/2,W).
+
+    GPU: one launch of the colour kernel on the current stream
+    (non-contiguous input is made contiguous first). CPU tensors and
+    AIRTC_FORCE_EAGER=1 take the torch integer reference. `out`, when given,
+    is written in place (contiguous u8 of the result shape)."""
+    _check_rgb_for_i420(x, torch.uint8)
+    xb, squeeze = _batched(x, 3)
+    b, h, w, _ = xb.shape
+    ob = None if out is None else (out.unsqueeze(0) if squeeze else out)
+    _check_out(ob, x, (b, h // 2 * 3, w))
+    if _on_kernel(x):
+        res = _require_ext().rgb_u8_to_i420(xb.contiguous(), ob)
+    else:
+        res = _rgb_u8_to_i420_ref(xb)
+        if ob is not None:
+            ob.copy_(res)
+    return _finish(res, out, squeeze)
+
+
+def postprocess_to_i420(img: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Image (H,W,3) / (B,H,W,3) in [-1,1] -> I420, bit for bit
+    rgb_u8_to_i420(postprocess_to_u8(img)).
+
+    GPU f16: ONE kernel (postprocess_to_u8's rounding fused with the colour
+    conversion, so the engine's decode graph gains no launch). Everything
+    else (CPU, f32, AIRTC_FORCE_EAGER=1) composes the two references."""
+    _check_rgb_for_i420(img, None)
+    xb, squeeze = _batched(img, 3)
+    b, h, w, _ = xb.shape
+    ob = None if out is None else (out.unsqueeze(0) if squeeze else out)
+    _check_out(ob, img, (b, h // 2 * 3, w))
+    if _use_hip(img):
+        res = _require_ext().postprocess_i420(xb.contiguous(), ob)
+    else:
+        u8 = (xb.float() + 1.0) * 127.5
+        res = _rgb_u8_to_i420_ref(u8.round().clamp(0, 255).to(torch.uint8))
+        if ob is not None:
+            ob.copy_(res)
+    return _finish(res, out, squeeze)
+
+
+def i420_to_rgb_u8(x: torch.Tensor, H: int | None = None,
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+    """I420 (3H/2,W) / (B,3H/2,W) -> u8 RGB (H,W,3) / (B,H,W,3).
+
+    H is implied by the shape; pass it to have it checked. Dispatch and
+    `out` as in rgb_u8_to_i420."""
+    _check_i420(x)
+    h, w = i420_size(x)
+    if H is not None and H != h:
+        raise ValueError(f"H={H} does not match the frame's {h} rows")
+    xb, squeeze = _batched(x, 2)
+    ob = None if out is None else (out.unsqueeze(0) if squeeze else out)
+    _check_out(ob, x, (xb.shape[0], h, w, 3))
+    if _on_kernel(x):
+        res = _require_ext().i420_to_rgb_u8(xb.contiguous(), ob)
+    else:
+        res = _i420_to_rgb_u8_ref(xb)
+        if ob is not None:
+            ob.copy_(res)
+    return _finish(res, out, squeeze)
