@@ -741,8 +741,22 @@ pybind11::tuple fp8_cvt_probe(torch::Tensor fin, double scale,
 
 void airtc_register_dtls(pybind11::module_& m);  // dtls.cpp
 
+// gemm_lt.cpp: x·Wᵀ + bias + residual as one hipBLASLt call
+torch::Tensor airtc_linear_residual(const torch::Tensor& x,
+                                    const torch::Tensor& weight,
+                                    const c10::optional<torch::Tensor>& bias,
+                                    const torch::Tensor& residual);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   airtc_register_dtls(m);
+  m.def("linear_residual", &airtc_linear_residual,
+        "x (...,K) · weight (N,K)ᵀ + bias (N,) + residual in one hipBLASLt "
+        "call (bias epilogue, C = residual, beta = 1); contiguous f16, fp32 "
+        "accumulation",
+        pybind11::arg("x"), pybind11::arg("weight"), pybind11::arg("bias"),
+        pybind11::arg("residual"));
+  // how the error for a shape the library has no algorithm for begins
+  m.attr("LT_NO_ALGORITHM") = "linear_residual: no hipBLASLt algorithm";
   m.def("conv2d", &conv2d, "implicit-GEMM MFMA conv2d (NHWC)",
         pybind11::arg("x"), pybind11::arg("w_perm"), pybind11::arg("bias"),
         pybind11::arg("cbias"), pybind11::arg("residual"), pybind11::arg("R"),

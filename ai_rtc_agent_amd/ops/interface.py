@@ -478,11 +478,17 @@ def linear(
     bias: torch.Tensor | None = None,
     residual: torch.Tensor | None = None,
 ) -> torch.Tensor:
-    """Linear projection. Plain GEMMs go to hipBLASLt (allowed: library
-    GEMMs); projections that carry a residual add (attention out-proj, FF
-    out, transformer proj_out) run through OUR MFMA kernel as a 1x1 conv
-    with the residual fused into the epilogue — one kernel instead of
-    GEMM + aten add."""
+    """Linear projection on hipBLASLt (allowed: library GEMMs).
+
+    Projections that carry a residual add (attention out-proj, FF out,
+    transformer proj_out) run as ONE library call on the GPU: the bias
+    rides in the GEMM's bias epilogue and the residual is its C operand
+    with beta = 1 (ops/csrc/gemm_lt.cpp), so the separate aten add and its
+    second f16 rounding disappear. x, weight, bias and residual must be
+    contiguous f16 there; a strided one raises, it is not copied.
+    AIRTC_LT_EPILOGUE=0 restores F.linear + add.
+    AIRTC_FUSED_PROJ=1 runs these projections through OUR MFMA kernel as a
+    1x1 conv with the residual fused into its epilogue instead."""
     # Measured on MI355X: hipBLASLt + the trailing aten add beats this fused
     # path at SD shapes (118 -> 109 fps when enabled); keep it opt-in until
     # the MFMA GEMM closes the gap (AIRTC_FUSED_PROJ=1).
@@ -499,9 +505,53 @@ def linear(
             residual.reshape(b, l, 1, -1).contiguous(), 1, 1, 1, 0, ACT_NONE,
         )
         return y.reshape(b, l, -1)
+    if residual is not None and _use_hip(x) \
+            and os.environ.get("AIRTC_LT_EPILOGUE") != "0":
+        y = _linear_residual_lt(x, weight, bias, residual)
+        if y is not None:
+            return y
     y = F.linear(x, weight, bias)
     if residual is not None:
         y = y + residual
+    return y
+
+
+# (M, N, K, has_bias) problems that stay on F.linear + add: those measured
+# slower as one call than as two (tools/kernel_bench.py "linear + residual",
+# profiles/optimization_ladder.md) ...
+_LT_UNFUSED_SHAPES: frozenset = frozenset()
+# ... and those hipBLASLt offered no algorithm for when first met
+_LT_NO_ALGO: set = set()
+_LT_SEEN: set = set()
+
+
+def _linear_residual_lt(x, weight, bias, residual):
+    """x·Wᵀ + bias + residual as one hipBLASLt call, or None where the
+    problem belongs on the two-kernel path. The path is picked up front by
+    shape and dtype; anything the native call rejects after that raises."""
+    fn = getattr(_require_ext(), "linear_residual", None)
+    if fn is None or weight.dtype != torch.float16 \
+            or residual.dtype != torch.float16 \
+            or (bias is not None and bias.dtype != torch.float16):
+        return None
+    n, k = weight.shape
+    key = (x.numel() // k, n, k, bias is not None)
+    if key in _LT_UNFUSED_SHAPES or key in _LT_NO_ALGO:
+        return None
+    if key in _LT_SEEN:
+        return fn(x, weight, bias, residual)
+    try:
+        y = fn(x, weight, bias, residual)
+    except RuntimeError as e:
+        # only "the library has no algorithm for this problem", only on the
+        # first call for a shape and never inside a graph capture, where the
+        # two paths would bake different kernels into the graph unnoticed
+        if _require_ext().LT_NO_ALGORITHM not in str(e) \
+                or torch.cuda.is_current_stream_capturing():
+            raise
+        _LT_NO_ALGO.add(key)
+        return None
+    _LT_SEEN.add(key)
     return y
 
 

@@ -17,7 +17,7 @@ CSRC = os.path.join(ROOT, "ai_rtc_agent_amd", "ops", "csrc")
 
 sources = [
     os.path.join(CSRC, f)
-    for f in ["ext.cpp", "vcn.cpp", "h264sw.cpp", "dtls.cpp", "elementwise.hip", "color.hip", "norms.hip", "conv2d.hip", "attention.hip", "fp8.hip", "conv2d_fp8.hip"]
+    for f in ["ext.cpp", "vcn.cpp", "h264sw.cpp", "dtls.cpp", "gemm_lt.cpp", "elementwise.hip", "color.hip", "norms.hip", "conv2d.hip", "attention.hip", "fp8.hip", "conv2d_fp8.hip"]
 ]
 
 setup(
@@ -26,7 +26,10 @@ setup(
         CUDAExtension(
             name="ai_rtc_agent_amd.ops._C",
             sources=sources,
-            libraries=["ssl", "crypto"],  # dtls.cpp (system OpenSSL 3)
+            # ssl/crypto: dtls.cpp (system OpenSSL 3). hipblaslt: gemm_lt.cpp;
+            # torch/lib comes first on the link path, so this resolves to the
+            # copy torch itself loads: one hipBLASLt per process
+            libraries=["ssl", "crypto", "hipblaslt"],
             extra_compile_args={
                 "cxx": ["-O3"],
                 "nvcc": ["-O3", "--offload-arch=gfx950", "-std=c++17"],

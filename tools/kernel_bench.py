@@ -10,12 +10,14 @@ from __future__ import annotations
 
 import argparse
 import os
+import statistics
 import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch
+import torch.nn.functional as F
 
 from ai_rtc_agent_amd import ops
 
@@ -41,6 +43,16 @@ ATTN_SHAPES = [
     ("cross 1024x77 c640", 1, 1024, 77, 640, 10),
 ]
 
+LINEAR_RES_SHAPES = [
+    # (M, N, K): every projection of the headline UNet (SD-Turbo 512x512,
+    # batch 1) that closes with a residual add. K = N: attention
+    # out-projections and proj_out; K = 4N: feed-forward out
+    (4096, 320, 320), (4096, 320, 1280),
+    (1024, 640, 640), (1024, 640, 2560),
+    (256, 1280, 1280), (256, 1280, 5120),
+    (64, 1280, 1280), (64, 1280, 5120),
+]
+
 
 def timeit(fn, iters):
     for _ in range(5):
@@ -53,14 +65,81 @@ def timeit(fn, iters):
     return (time.perf_counter() - t0) / iters * 1e6  # us
 
 
+def window_us(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3 / iters
+
+
+def captured(fn, iters):
+    """`iters` back-to-back calls of fn as one hipGraph: replaying it times
+    the device work without the host's launch cost, as in the engine's
+    captured frame."""
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(iters):
+            fn()
+    return graph.replay
+
+
+def bench_linear_residual(iters, reps=9):
+    """F.linear + aten add against the one-call hipBLASLt epilogue
+    (ops.linear, AIRTC_LT_EPILOGUE): device events around `iters`
+    back-to-back calls, `reps` windows per side, sides alternating; median
+    and min..max per call. Two rows per shape: eager calls (at these sizes
+    the host's launch cost bounds them) and the same calls replayed from a
+    hipGraph (device time, what the captured frame pays)."""
+    dev = "cuda"
+    ext = ops.hip_ext()
+    print("== linear + residual (pair = F.linear + aten add, fused = one "
+          "hipBLASLt call: bias epilogue, C = residual, beta = 1) ==")
+    print(f"  {'M x N x K':>18s} {'mode':>6s}  {'pair us (min..max)':>24s}  "
+          f"{'fused us (min..max)':>24s}  fused/pair  verdict")
+    for m, n, k in LINEAR_RES_SHAPES:
+        g = torch.Generator().manual_seed(m + n + k)
+        x = (torch.randn(1, m, k, generator=g) / k ** 0.5).half().to(dev)
+        w = (torch.randn(n, k, generator=g) / k ** 0.5).half().to(dev)
+        bias = torch.randn(n, generator=g).half().to(dev)
+        res = torch.randn(1, m, n, generator=g).half().to(dev)
+        pair = lambda: F.linear(x, w, bias) + res
+        fused = lambda: ext.linear_residual(x, w, bias, res)
+        for fn in (pair, fused):
+            for _ in range(20):
+                fn()
+        torch.cuda.synchronize()
+        sides = {"eager": (pair, fused, iters),
+                 "graph": (captured(pair, iters), captured(fused, iters), 1)}
+        for mode, (fp, ff, calls) in sides.items():
+            t_p, t_f = [], []
+            for _ in range(reps):
+                t_p.append(window_us(fp, calls) * calls / iters)
+                t_f.append(window_us(ff, calls) * calls / iters)
+            mp, mf = statistics.median(t_p), statistics.median(t_f)
+            # slower only counts beyond the side's own min..max spread
+            slower = mf - mp > max(t_f) - min(t_f)
+            print(f"  {f'{m} x {n} x {k}':>18s} {mode:>6s}  "
+                  f"{f'{mp:7.2f} ({min(t_p):.2f}..{max(t_p):.2f})':>24s}  "
+                  f"{f'{mf:7.2f} ({min(t_f):.2f}..{max(t_f):.2f})':>24s}  "
+                  f"{mf / mp:10.3f}  {'SLOWER' if slower else 'ok'}")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--iters", type=int, default=50)
     p.add_argument("--batch", type=int, default=1,
                    help="scale conv batch (the fbs>1 serving tier)")
+    p.add_argument("--only", choices=["linear"],
+                   help="run one group: linear = linear + residual")
     args = p.parse_args()
     assert torch.cuda.is_available(), "GPU microbench"
     dev = "cuda"
+    if args.only == "linear":
+        bench_linear_residual(max(args.iters, 200))
+        return
 
     print(f"== conv2d (NHWC implicit-GEMM MFMA) B={args.batch} ==")
     for name, b0, h, w, ic, oc, k, st in CONV_SHAPES:
@@ -173,6 +252,8 @@ def main():
     u8 = torch.randint(0, 256, (1, 512, 512, 3), dtype=torch.uint8, device=dev)
     us = timeit(lambda: ops.preprocess_from_u8(u8, torch.float16), args.iters)
     print(f"  {'preprocess 512x512':32s} {us:8.1f} us  {u8.numel()*3/us/1e3:7.1f} GB/s")
+
+    bench_linear_residual(max(args.iters, 200))
 
 
 if __name__ == "__main__":
