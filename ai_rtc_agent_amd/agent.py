@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import argparse
 import logging
+import math
 import os
 import uuid
 from typing import Optional
@@ -50,11 +51,12 @@ async def offer(request: web.Request) -> web.Response:
     pc = PeerConnection(ice_servers=st["ice_servers"])
     st["pcs"].add(pc)
     pipeline = st["pool"].assign(stream_id)
+    st.setdefault("session_pipelines", {})[stream_id] = pipeline
     events: StreamEventHandler = st["events"]
 
     @pc.on("datachannel_message")
     def on_config(msg: dict) -> None:
-        _apply_config(pipeline, msg)
+        _apply_session_config(pipeline, msg)
 
     @pc.on("track")
     def on_track(track) -> None:
@@ -70,6 +72,7 @@ async def offer(request: web.Request) -> web.Response:
         elif pc.connection_state in ("failed", "closed"):
             st["pcs"].discard(pc)
             st["pool"].release(stream_id)
+            st.get("session_pipelines", {}).pop(stream_id, None)
             if pc.connection_state == "closed":
                 await events.stream_ended(stream_id, room_id)
 
@@ -90,11 +93,12 @@ async def whip(request: web.Request) -> web.Response:
     pc = PeerConnection()
     st["pcs"].add(pc)
     pipeline = st["pool"].assign(stream_id)
+    st.setdefault("session_pipelines", {})[stream_id] = pipeline
     events: StreamEventHandler = st["events"]
 
     @pc.on("datachannel_message")
     def on_config(msg: dict) -> None:
-        _apply_config(pipeline, msg)
+        _apply_session_config(pipeline, msg)
 
     @pc.on("track")
     def on_track(track) -> None:
@@ -108,6 +112,7 @@ async def whip(request: web.Request) -> web.Response:
         elif pc.connection_state in ("failed", "closed"):
             st["pcs"].discard(pc)
             st["pool"].release(stream_id)
+            st.get("session_pipelines", {}).pop(stream_id, None)
             if st.get("whip_pc") is pc:
                 st["source_track"] = None
                 st["whip_pc"] = None
@@ -139,6 +144,7 @@ async def whip_delete(request: web.Request) -> web.Response:
             st["whip_pc"] = None
             st["source_track"] = None
         st["pool"].release(sid)
+        st.get("session_pipelines", {}).pop(sid, None)
         return web.Response(status=200)
     pc = st.get("whip_pc")
     if pc is not None:
@@ -190,20 +196,90 @@ async def whep_delete(request: web.Request) -> web.Response:
     return web.Response(status=200)
 
 
+def _checked_config(params) -> dict:
+    """The recognised keys of a config message, type-checked; ValueError on
+    a malformed value (HTTP answers 400, the datachannel logs and ignores)."""
+    if not isinstance(params, dict):
+        raise ValueError("config must be a JSON object")
+    out = {}
+    t = params.get("t_index_list")
+    if t is not None:
+        if (not isinstance(t, (list, tuple)) or not t
+                or any(isinstance(v, bool) or not isinstance(v, int) for v in t)):
+            raise ValueError("t_index_list must be a non-empty list of integers")
+        out["t_index_list"] = list(t)
+    for key in ("prompt", "negative_prompt"):
+        v = params.get(key)
+        if v is not None:
+            if not isinstance(v, str):
+                raise ValueError(f"{key} must be a string")
+            out[key] = v
+    for key in ("guidance_scale", "delta"):
+        v = params.get(key)
+        if v is not None:
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError(f"{key} must be a finite number")
+            out[key] = float(v)
+    return out
+
+
 def _apply_config(pipeline, params: dict) -> None:
     """Shared by POST /config and the datachannel messages
-    (reference agent.py:154-168, 324-337, 398-412)."""
-    if "t_index_list" in params and params["t_index_list"] is not None:
-        pipeline.update_t_index_list(params["t_index_list"])
-    if "prompt" in params and params["prompt"] is not None:
-        pipeline.update_prompt(params["prompt"])
+    (reference agent.py:154-168, 324-337, 398-412). A session's datachannel
+    hands in its own pipeline — for a batched replica its SlotProxy, so the
+    update reaches that session alone. Raises ValueError on malformed
+    values (including what the pipeline itself rejects, such as a
+    per-session t_index_list of another length)."""
+    _apply_checked(pipeline, _checked_config(params))
+
+
+def _apply_checked(pipeline, cfg: dict) -> None:
+    """Apply a type-checked config, key by key. The pipeline itself may
+    still reject a value (ValueError): a per-session t_index_list of another
+    length, a per-session guidance raise on an engine without
+    runtime_guidance. Keys applied before the rejected one stay applied."""
+    if "t_index_list" in cfg:
+        pipeline.update_t_index_list(cfg["t_index_list"])
+    if "prompt" in cfg:
+        pipeline.update_prompt(cfg["prompt"])
+    if "negative_prompt" in cfg:
+        pipeline.update_negative_prompt(cfg["negative_prompt"])
+    if "guidance_scale" in cfg or "delta" in cfg:
+        pipeline.update_guidance(cfg.get("guidance_scale"), cfg.get("delta"))
+
+
+def _apply_session_config(pipeline, msg) -> None:
+    """Datachannel form: a malformed message is logged and ignored."""
+    try:
+        _apply_config(pipeline, msg)
+    except ValueError as e:
+        logger.warning("ignored config message: %s", e)
 
 
 async def update_config(request: web.Request) -> web.Response:
-    params = await request.json()
+    """POST /config. With "stream_id" (the id in the WHIP Location header)
+    that session alone is updated — 404 when it is unknown; without it every
+    active pipeline is. Malformed values answer 400: a wrong type before
+    anything is touched, a value the pipeline rejects (_apply_checked) after
+    the keys that precede it were applied."""
+    try:
+        params = await request.json()
+    except ValueError:
+        return web.json_response({"error": "body must be JSON"}, status=400)
     st = _state(request.app)
-    for pipeline in st["pool"].active():
-        _apply_config(pipeline, params)
+    sid = params.get("stream_id") if isinstance(params, dict) else None
+    if sid is not None:
+        targets = [st.get("session_pipelines", {}).get(sid)]
+        if targets[0] is None:
+            return web.json_response({"error": f"unknown stream_id {sid!r}"}, status=404)
+    else:
+        targets = st["pool"].active()
+    try:
+        cfg = _checked_config(params)  # reject before any pipeline is touched
+        for pipeline in targets:
+            _apply_checked(pipeline, cfg)
+    except ValueError as e:
+        return web.json_response({"error": str(e)}, status=400)
     return web.json_response({"status": "ok"})
 
 
@@ -366,6 +442,11 @@ def main() -> None:
                              "colour conversion runs on the GPU and the "
                              "codec reads/writes its planes directly "
                              "(same as AIRTC_MEDIA_YUV=1)")
+    parser.add_argument("--runtime-guidance", action="store_true",
+                        help="keep the RCFG step in the captured graph "
+                             "whatever the initial guidance_scale, so a "
+                             "session can raise its guidance at runtime "
+                             "(same as AIRTC_RUNTIME_GUIDANCE=1)")
     parser.add_argument("--streams-per-gpu", type=int, default=1,
                         help="multi-stream batched serving: sessions per "
                              "GPU batched through one engine (fbs=K; "
@@ -383,6 +464,9 @@ def main() -> None:
         # read by config.media_yuv() (codec selection, EngineConfig's
         # output_format default) here and in spawned workers
         os.environ["AIRTC_MEDIA_YUV"] = "1"
+    if args.runtime_guidance:
+        # read by EngineConfig.runtime_guidance here and in spawned workers
+        os.environ["AIRTC_RUNTIME_GUIDANCE"] = "1"
     ports = None
     if args.udp_ports:
         lo, _, hi = args.udp_ports.partition("-")

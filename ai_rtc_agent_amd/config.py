@@ -50,6 +50,9 @@ def _env_float(name: str, default: float) -> float:
 #                                        of packed RGB (codec plane I/O, GPU
 #                                        colour conversion); also the default
 #                                        of EngineConfig.output_format
+# AIRTC_RUNTIME_GUIDANCE (0|1)       -> EngineConfig.runtime_guidance: keep
+#                                        the RCFG step in the captured graph
+#                                        so guidance can be raised at runtime
 
 
 def engines_cache_dir() -> str:
@@ -178,6 +181,13 @@ class EngineConfig:
     # u8 planes ready for the codec (needs even height and width). Input
     # frames may be either format whatever this says.
     output_format: str = field(default_factory=lambda: "i420" if media_yuv() else "rgb")
+
+    # keep the RCFG step (and for cfg full/initialize its extra UNet rows) in
+    # the captured graph whatever the initial guidance_scale, so that
+    # update_guidance() can raise guidance later, per serving slot, without
+    # a re-capture. Off: an engine prepared with guidance_scale <= 1 has no
+    # guidance math in its hot path at all (the benchmarked graphs).
+    runtime_guidance: bool = field(default_factory=lambda: _env_bool("AIRTC_RUNTIME_GUIDANCE", False))
 
     def __post_init__(self) -> None:
         if self.output_format not in OUTPUT_FORMATS:

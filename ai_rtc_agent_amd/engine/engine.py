@@ -23,6 +23,7 @@ from __future__ import annotations
 
 from typing import Optional, Sequence
 
+import contextlib
 import logging
 import math
 import os
@@ -35,7 +36,7 @@ from ..models.lora import fuse_lora_state_dict, load_lora_file, make_random_lora
 from ..utils.timers import StageTimers
 from .. import ops
 from .rcfg import ResidualCFG
-from .scheduler import StreamScheduler
+from .scheduler import StreamScheduler, slot_rows
 from .similarity import StochasticSimilarityFilter
 
 
@@ -70,7 +71,8 @@ class StreamDiffusionEngine:
         torch.manual_seed(cfg.seed)
 
         self.scheduler = StreamScheduler(num_inference_steps=cfg.num_inference_steps)
-        self.rcfg = ResidualCFG(cfg.cfg_type, cfg.guidance_scale, cfg.delta)
+        self.rcfg = ResidualCFG(cfg.cfg_type, cfg.guidance_scale, cfg.delta,
+                                runtime=cfg.runtime_guidance)
         self.sim_filter: Optional[StochasticSimilarityFilter] = None
         if cfg.similarity_filter.enabled:
             gen = torch.Generator().manual_seed(cfg.seed)
@@ -221,7 +223,8 @@ class StreamDiffusionEngine:
             self.scheduler = StreamScheduler(num_inference_steps=num_inference_steps)
         if guidance_scale is not None:
             cfg.guidance_scale = guidance_scale
-            self.rcfg = ResidualCFG(cfg.cfg_type, guidance_scale, cfg.delta)
+            self.rcfg = ResidualCFG(cfg.cfg_type, guidance_scale, cfg.delta,
+                                    runtime=cfg.runtime_guidance)
         if t_index_list is not None:
             cfg.t_index_list = list(t_index_list)
 
@@ -262,6 +265,9 @@ class StreamDiffusionEngine:
         self._src_size: list = [None] * fbs
         # "rgb" / "i420" as last handed in per slot
         self._src_format: list = [None] * fbs
+        # per-slot runtime controls, host side (slot_controls()/stats): every
+        # slot starts from the replica defaults
+        self._slot_ctl: list = [self._slot_defaults() for _ in range(fbs)]
         self._ts_batch = self._coeff["sub_timesteps_tensor"].to(dev)
         self._prev_out: Optional[torch.Tensor] = None
         self._graph = None
@@ -300,18 +306,23 @@ class StreamDiffusionEngine:
                 cur.copy_(kv)
 
     @torch.no_grad()
-    def _refresh_added_cond(self) -> None:
-        """(Re)compute the sdxl addition-embedding into its static buffer."""
+    def _added_cond_vec(self, prompt: str) -> torch.Tensor:
+        """The sdxl addition-embedding (1, addition_embed_dim) of a prompt."""
         from ..models.unet import timestep_embedding
 
         cfg = self.cfg
-        pooled = self.text_encoder.pooled(self.prompt, self.device, self.dtype)
+        pooled = self.text_encoder.pooled(prompt, self.device, self.dtype)
         ids = torch.tensor(
             [cfg.height, cfg.width, 0, 0, cfg.height, cfg.width],
             dtype=torch.float32, device=self.device,
         )
         time_emb = timestep_embedding(ids, 256).flatten()[None].to(self.dtype)
-        vec = torch.cat([pooled, time_emb], dim=-1)
+        return torch.cat([pooled, time_emb], dim=-1)
+
+    @torch.no_grad()
+    def _refresh_added_cond(self) -> None:
+        """(Re)compute the sdxl addition-embedding into its static buffer."""
+        vec = self._added_cond_vec(self.prompt)
         self._added_cond.copy_(vec.expand_as(self._added_cond))
 
     # ------------------------------------------------------------------
@@ -368,55 +379,337 @@ class StreamDiffusionEngine:
 
     # ------------------------------------------------------------------
     # runtime config updates (POST /config + datachannel)
+    #
+    # Every updater takes slot=None (every slot: the replica-wide update,
+    # which also moves the defaults reset_slot() restores) or one serving
+    # slot, whose rows alone are rewritten (row law: scheduler.slot_rows).
     # ------------------------------------------------------------------
-    @torch.no_grad()
-    def update_prompt(self, prompt: str) -> None:
-        """Re-encode the prompt and overwrite the cached embeddings IN PLACE
-        (graph-external buffer update; reference lib/pipeline.py:44-45)."""
-        self.prompt = prompt
-        emb = self.text_encoder.encode(prompt, self.device, self.dtype)
-        self._embeds.copy_(emb)
-        self._embeds_batch.copy_(emb.expand_as(self._embeds_batch))
-        if self.cfg.cfg_type == "full":
-            B = self._embeds_batch.shape[0]
-            self._embeds_full[B:].copy_(self._embeds_batch)
-        if self._added_cond is not None:
-            self._refresh_added_cond()
-            self._refresh_temb_static()  # added-cond feeds the static temb
-        self._refresh_static_kv()
+    def _slot_defaults(self) -> dict:
+        cfg = self.cfg
+        return {
+            "prompt": self.prompt,
+            "negative_prompt": cfg.negative_prompt,
+            "guidance_scale": float(cfg.guidance_scale),
+            "delta": float(cfg.delta),
+            "t_index_list": list(cfg.t_index_list),
+        }
+
+    def _set_ctl(self, slot: Optional[int], **kw) -> None:
+        for c in (self._slot_ctl if slot is None else [self._slot_ctl[slot]]):
+            c.update(kw)
+
+    def _check_slot(self, slot: Optional[int]) -> None:
+        assert self._prepared, "call prepare() first"
+        fbs = self.cfg.frame_buffer_size
+        if slot is not None and not (isinstance(slot, int) and 0 <= slot < fbs):
+            raise ValueError(f"slot must be an int in [0, {fbs}), got {slot!r}")
+
+    def slot_controls(self, slot: int) -> dict:
+        """The slot's current prompt, negative_prompt, guidance_scale, delta
+        and t_index_list (host-side copies; nothing is read from the GPU)."""
+        self._check_slot(slot)
+        c = dict(self._slot_ctl[slot])
+        c["t_index_list"] = list(c["t_index_list"])
+        return c
+
+    def _layout(self) -> str:
+        """UNet batch layout: "full" = [uncond x B | cond x B], "initialize"
+        = [seed x fbs | B], "plain" = the B stream-batch rows."""
+        if self.cfg.cfg_type in ("full", "initialize") and self.rcfg.active:
+            return self.cfg.cfg_type
+        return "plain"
+
+    @contextlib.contextmanager
+    def _row_writes(self, *produced: torch.Tensor):
+        """Order in-place writes of graph-read buffers against the replays.
+        With pipelined graphs the denoise graph replays on stream A while
+        the caller's stream runs ahead, so the writes are enqueued on
+        stream A after it waits for the caller's stream (which ran the text
+        encoder and produced `produced`): a replay sees a row entirely old
+        or entirely new. No host sync. Otherwise (eager, single graph, CPU)
+        replays run on the caller's stream and program order is enough."""
+        if (self.device.type == "cuda" and self._graph is not None
+                and self._pipelined):
+            cur = torch.cuda.current_stream()
+            with torch.cuda.stream(self._sA):
+                self._sA.wait_stream(cur)
+                for t in produced:
+                    # allocated on the caller's stream, read on stream A:
+                    # without this the caller's next allocation could reuse
+                    # the block before stream A (a frame behind) has read it
+                    if t.is_cuda:
+                        t.record_stream(self._sA)
+                yield
+        else:
+            yield
+
+    def _write_slot_kv(self, emb: torch.Tensor, slot: Optional[int],
+                       uncond: bool = False) -> None:
+        """K|V of ONE prompt (a 1-row GEMM per cross-attention layer) into
+        the slot's rows of every static_kv. In the full layout the prompt
+        owns the cond half and the negative prompt (uncond=True) the uncond
+        half; in the others every row of the slot reads the prompt."""
+        fbs = self.cfg.frame_buffer_size
+        layout = self._layout()
+        if uncond and layout != "full":
+            return
+        for m in self._cross_attn_modules():
+            kv = m.static_kv
+            if layout == "full":
+                half = kv.shape[0] // 2
+                kv = kv[:half] if uncond else kv[half:]
+            slot_rows(kv, slot, fbs).copy_(m.compute_kv(emb))
 
     @torch.no_grad()
-    def update_t_index_list(self, t_index_list: Sequence[int]) -> None:
+    def update_prompt(self, prompt: str, slot: Optional[int] = None) -> None:
+        """Re-encode the prompt and overwrite the cached embeddings IN PLACE
+        (graph-external buffer update; reference lib/pipeline.py:44-45)."""
+        self._check_slot(slot)
+        emb = self.text_encoder.encode(prompt, self.device, self.dtype)
+        if slot is not None:
+            fbs = self.cfg.frame_buffer_size
+            vec = (self._added_cond_vec(prompt)
+                   if self._added_cond is not None else None)
+            with self._row_writes(emb, *([] if vec is None else [vec])):
+                slot_rows(self._embeds_batch, slot, fbs).copy_(emb)
+                if self.cfg.cfg_type == "full":
+                    B = self._embeds_batch.shape[0]
+                    slot_rows(self._embeds_full[B:], slot, fbs).copy_(emb)
+                self._write_slot_kv(emb, slot)
+                if vec is not None:
+                    slot_rows(self._added_cond, slot, fbs).copy_(vec)
+                    # same inputs give the other rows the values they hold
+                    self._refresh_temb_static()
+            self._set_ctl(slot, prompt=prompt)
+            return
+        self.prompt = prompt
+        self._set_ctl(None, prompt=prompt)
+        with self._row_writes(emb):
+            self._embeds.copy_(emb)
+            self._embeds_batch.copy_(emb.expand_as(self._embeds_batch))
+            if self.cfg.cfg_type == "full":
+                B = self._embeds_batch.shape[0]
+                self._embeds_full[B:].copy_(self._embeds_batch)
+            if self._added_cond is not None:
+                self._refresh_added_cond()
+                self._refresh_temb_static()  # added-cond feeds the static temb
+            self._refresh_static_kv()
+
+    @torch.no_grad()
+    def update_negative_prompt(self, prompt: str, slot: Optional[int] = None) -> None:
+        """The uncond prompt of cfg_type "full": rewrite the uncond rows of
+        the embeddings and their K|V in place. For every other cfg_type it
+        is only stored, as prepare() only reads it for "full"."""
+        self._check_slot(slot)
+        if slot is None:
+            self.cfg.negative_prompt = prompt
+        self._set_ctl(slot, negative_prompt=prompt)
+        if self.cfg.cfg_type != "full":
+            return
+        fbs = self.cfg.frame_buffer_size
+        emb = self.text_encoder.encode(prompt, self.device, self.dtype)
+        with self._row_writes(emb):
+            B = self._embeds_batch.shape[0]
+            slot_rows(self._embeds_full[:B], slot, fbs).copy_(emb)
+            self._write_slot_kv(emb, slot, uncond=True)
+
+    @torch.no_grad()
+    def update_guidance(self, guidance_scale: Optional[float] = None,
+                        delta: Optional[float] = None,
+                        slot: Optional[int] = None) -> None:
+        """Change guidance_scale and/or delta at runtime: an in-place write
+        of the RCFG step's per-row coefficients (never a re-capture). The
+        effective scale of a row is max(g, 1): g <= 1 passes its eps
+        through. When RCFG is not active it is not in the captured graph:
+        a replica-wide raise above 1 then re-prepares (as a length-changing
+        update_t_index_list does), and a per-slot raise is an error — start
+        with runtime_guidance=True to keep the step in the graph."""
+        self._check_slot(slot)
+        try:
+            g = None if guidance_scale is None else float(guidance_scale)
+            d = None if delta is None else float(delta)
+        except TypeError as e:
+            raise ValueError(f"guidance_scale and delta must be numbers: {e}") from e
+        if any(v is not None and not math.isfinite(v) for v in (g, d)):
+            raise ValueError("guidance_scale and delta must be finite")
+        cfg = self.cfg
+        kw = {}
+        if g is not None:
+            kw["guidance_scale"] = g
+        if d is not None:
+            kw["delta"] = d
+        if not self.rcfg.active:
+            if g is not None and g > 1.0 and cfg.cfg_type != "none":
+                if slot is not None:
+                    raise ValueError(
+                        "RCFG is not in this engine's captured step (its "
+                        "guidance_scale was <= 1 at prepare()), so one slot "
+                        "cannot raise it: set runtime_guidance=True "
+                        "(AIRTC_RUNTIME_GUIDANCE=1) to keep the step in")
+                self._reprepare(guidance_scale=g, delta=d)
+                return
+            if slot is None:
+                if g is not None:
+                    cfg.guidance_scale = g
+                if d is not None:
+                    cfg.delta = d
+                self.rcfg.set_guidance(g, d)
+            self._set_ctl(slot, **kw)
+            return
+        with self._row_writes():
+            self.rcfg.set_guidance(g, d, slot, cfg.frame_buffer_size)
+        if slot is None:
+            if g is not None:
+                cfg.guidance_scale = g
+            if d is not None:
+                cfg.delta = d
+        self._set_ctl(slot, **kw)
+
+    def _reprepare(self, guidance_scale: Optional[float] = None,
+                   delta: Optional[float] = None,
+                   t_index_list: Optional[list] = None) -> None:
+        """A replica-wide update that needs prepare() again (another batch
+        shape, or RCFG entering the step). prepare() reallocates
+        graph-captured buffers (_coeff, _x_t_buffer, _frame_in) and drops
+        the graphs, so quiesce first: in-flight pipelined replays on streams
+        A/B must not read freed memory (the rule refresh_weights follows).
+        The stream-batch state restarts for every slot, but the sessions
+        keep their own controls: whatever a slot had moved away from the
+        replica default is written again afterwards (a t_index_list of the
+        old length cannot be; that slot takes the new default)."""
+        saved = [dict(c) for c in self._slot_ctl]
+        old = self._slot_defaults()
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        if delta is not None:
+            self.cfg.delta = delta
+        if t_index_list is not None:
+            self.cfg.t_index_list = list(t_index_list)
+        self.prepare(guidance_scale=guidance_scale)
+        n = len(self.cfg.t_index_list)
+        for slot, c in enumerate(saved[: self.cfg.frame_buffer_size]):
+            if c["prompt"] != old["prompt"]:
+                self.update_prompt(c["prompt"], slot)
+            if c["negative_prompt"] != old["negative_prompt"]:
+                self.update_negative_prompt(c["negative_prompt"], slot)
+            g = c["guidance_scale"] if c["guidance_scale"] != old["guidance_scale"] else None
+            d = c["delta"] if c["delta"] != old["delta"] else None
+            if g is not None or d is not None:
+                self.update_guidance(g, d, slot)
+            if c["t_index_list"] != old["t_index_list"] and len(c["t_index_list"]) == n:
+                self.update_t_index_list(c["t_index_list"], slot)
+
+    @staticmethod
+    def _tensors_of(coeff: dict) -> list:
+        return [v for v in coeff.values() if isinstance(v, torch.Tensor)]
+
+    def _update_slot_t_index_list(self, t_index_list: list, slot: int) -> None:
+        cfg = self.cfg
+        fbs = cfg.frame_buffer_size
+        if len(t_index_list) != len(cfg.t_index_list):
+            raise ValueError(
+                f"a per-slot t_index_list must keep the replica's length "
+                f"{len(cfg.t_index_list)}, got {len(t_index_list)}")
+        new = self.scheduler.coefficients(t_index_list, fbs, self.device, self.dtype)
+        new_ts = new["sub_timesteps_tensor"].to(self.device)
+        with self._row_writes(new_ts, *self._tensors_of(new)):
+            for k in ("alpha_prod_t_sqrt", "beta_prod_t_sqrt", "c_skip", "c_out",
+                      "alpha_f32", "beta_f32", "c_skip_f32", "c_out_f32"):
+                slot_rows(self._coeff[k], slot, fbs).copy_(slot_rows(new[k], slot, fbs))
+            slot_rows(self._ts_batch, slot, fbs).copy_(slot_rows(new_ts, slot, fbs))
+            # the batched-ts cache of cfg full/initialize is a separate cat
+            # buffer: same rows, in place (the static-temb fast path keys on
+            # the tensor's identity)
+            ts_unet = self._unet_batch_timesteps()
+            if ts_unet is not self._ts_batch:
+                lead = ts_unet.shape[0] - new_ts.shape[0]
+                src = torch.cat([new_ts[:lead], new_ts], dim=0)
+                slot_rows(ts_unet, slot, fbs).copy_(slot_rows(src, slot, fbs))
+            # same inputs give the other rows the values they hold
+            self._refresh_temb_static()
+        self._set_ctl(slot, t_index_list=list(t_index_list))
+
+    @torch.no_grad()
+    def reset_slot(self, slot: int) -> None:
+        """Hand a slot to a new session: its in-flight latents and RCFG
+        stock rows go back to their post-prepare() state and its controls
+        to the replica defaults, so nothing of the previous tenant is
+        decoded into the new session's frames. The next call is also never
+        a similarity-filter skip (_prev_out is dropped), since a skip would
+        return the previous tenant's last frame. Not touched: the pipelined
+        ping-pong output buffers, which hold the last frame decoded for this
+        slot until the slot's next frame replaces it; they are only ever
+        handed out as the result of a call, which overwrites them first."""
+        self._check_slot(slot)
+        if slot is None:
+            raise ValueError("reset_slot needs a slot")
+        fbs = self.cfg.frame_buffer_size
+        with self._row_writes():
+            if self._x_t_buffer.shape[0]:
+                slot_rows(self._x_t_buffer, slot, fbs).zero_()
+            stock = self.rcfg.stock_noise
+            if stock is not None and stock.shape == self._init_noise.shape:
+                slot_rows(stock, slot, fbs).copy_(slot_rows(self._init_noise, slot, fbs))
+        # controls: only what the previous tenant moved is rewritten
+        d, c = self._slot_defaults(), self._slot_ctl[slot]
+        if c["prompt"] != d["prompt"]:
+            self.update_prompt(d["prompt"], slot)
+        if c["negative_prompt"] != d["negative_prompt"]:
+            self.update_negative_prompt(d["negative_prompt"], slot)
+        if (c["guidance_scale"], c["delta"]) != (d["guidance_scale"], d["delta"]):
+            self.update_guidance(d["guidance_scale"], d["delta"], slot)
+        if c["t_index_list"] != d["t_index_list"]:
+            self.update_t_index_list(d["t_index_list"], slot)
+        self._prev_out = None
+        if slot < len(self._src_size):
+            self._src_size[slot] = None
+        if slot < len(self._src_format):
+            self._src_format[slot] = None
+
+    @torch.no_grad()
+    def update_t_index_list(self, t_index_list: Sequence[int],
+                            slot: Optional[int] = None) -> None:
         """Contract of reference lib/wrapper.py:389-407: no-op when
-        unchanged; length changes require prepare() (batch shape changes)."""
-        t_index_list = list(t_index_list)
-        if t_index_list == self.cfg.t_index_list:
+        unchanged; length changes require prepare() (batch shape changes).
+        A per-slot list must keep the length (ValueError otherwise)."""
+        self._check_slot(slot)
+        try:
+            t_index_list = [int(t) for t in t_index_list]
+        except TypeError as e:
+            raise ValueError(f"t_index_list must be a list of ints: {e}") from e
+        try:
+            self.scheduler.sub_timesteps(t_index_list)
+        except IndexError as e:
+            raise ValueError(
+                f"t_index_list {t_index_list} indexes outside the "
+                f"{len(self.scheduler.timesteps)}-step timetable") from e
+        if slot is not None:
+            if t_index_list != self._slot_ctl[slot]["t_index_list"]:
+                self._update_slot_t_index_list(t_index_list, slot)
+            return
+        if (t_index_list == self.cfg.t_index_list
+                and all(c["t_index_list"] == t_index_list for c in self._slot_ctl)):
             return
         if len(t_index_list) != len(self.cfg.t_index_list):
-            # prepare() reallocates graph-captured buffers (_coeff, _x_t_buffer,
-            # _frame_in) and drops the graphs; quiesce first so in-flight
-            # pipelined replays on streams A/B are not reading freed memory
-            # (same rule refresh_weights follows).
-            if self.device.type == "cuda":
-                torch.cuda.synchronize(self.device)
-            self.cfg.t_index_list = t_index_list
-            self.prepare()
+            self._reprepare(t_index_list=t_index_list)
             return
         self.cfg.t_index_list = t_index_list
+        self._set_ctl(None, t_index_list=list(t_index_list))
         new = self.scheduler.coefficients(
             t_index_list, self.cfg.frame_buffer_size, self.device, self.dtype
         )
-        for k in ("alpha_prod_t_sqrt", "beta_prod_t_sqrt", "c_skip", "c_out"):
-            self._coeff[k].copy_(new[k])
-        self._coeff["sub_timesteps"] = new["sub_timesteps"]
-        self._ts_batch.copy_(new["sub_timesteps_tensor"].to(self.device))
-        for k in ("alpha_f32", "beta_f32", "c_skip_f32", "c_out_f32"):
-            self._coeff[k].copy_(new[k].to(self.device))
-        # static time-embedding caches follow the new timesteps (in place —
-        # any captured graph reads the same storage). The batched-ts cache
-        # is a SEPARATE cat buffer for cfg full/initialize: rebuild it.
-        self._ts_unet_cache = None
-        self._refresh_temb_static()
+        with self._row_writes(*self._tensors_of(new)):
+            for k in ("alpha_prod_t_sqrt", "beta_prod_t_sqrt", "c_skip", "c_out"):
+                self._coeff[k].copy_(new[k])
+            self._coeff["sub_timesteps"] = new["sub_timesteps"]
+            self._ts_batch.copy_(new["sub_timesteps_tensor"].to(self.device))
+            for k in ("alpha_f32", "beta_f32", "c_skip_f32", "c_out_f32"):
+                self._coeff[k].copy_(new[k].to(self.device))
+            # static time-embedding caches follow the new timesteps (in place —
+            # any captured graph reads the same storage). The batched-ts cache
+            # is a SEPARATE cat buffer for cfg full/initialize: rebuild it.
+            self._ts_unet_cache = None
+            self._refresh_temb_static()
 
     # ------------------------------------------------------------------
     # core step (graph-capturable: static shapes, static buffers)

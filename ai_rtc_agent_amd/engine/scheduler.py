@@ -21,6 +21,24 @@ from typing import List, Sequence
 import torch
 
 
+def slot_rows(t: torch.Tensor, slot: int | None, fbs: int) -> torch.Tensor:
+    """The row law, in one place: the view of `t`'s rows that belong to one
+    serving slot (every row when slot is None).
+
+    Stream-batch rows are stage-major, row = stage * fbs + slot (fbs =
+    frame_buffer_size; see repeat_interleave in coefficients() below). The
+    UNet batch layouts stack whole multiples of fbs on top of that
+    ([uncond x B | cond x B] for cfg full, [seed x fbs | B] for initialize),
+    so in every layout a slot owns exactly the rows with row % fbs == slot."""
+    if slot is None:
+        return t
+    if not 0 <= slot < fbs:
+        raise ValueError(f"slot must be in [0, {fbs}), got {slot}")
+    if t.shape[0] % fbs:
+        raise ValueError(f"{t.shape[0]} rows are no multiple of fbs={fbs}")
+    return t[slot::fbs]
+
+
 class StreamScheduler:
     """Precomputes per-sub-timestep coefficients for stream-batch denoising."""
 

@@ -256,6 +256,129 @@ extern "C" void airtc_sched_blend(const uint16_t* xt, const uint16_t* eps,
 }
 
 // ---------------------------------------------------------------------------
+// rcfg_apply: the residual-CFG step in ONE launch, coefficients per batch row
+// from f32 device arrays (rewritten in place under a captured graph — one
+// serving slot changes its guidance without touching the others). Replaces
+// the ~6 aten launches of ResidualCFG.apply + _shift_stock. B = output rows.
+//   SELF: out[r] = eps[r] + gm1[r]*(eps[r] - delta[r]*stock[r])
+//         stock[r] <- eps[r] (r < fbs) | eps[r-fbs]          (the stage shift)
+//   INIT: eps = [seed(fbs) | eps_c(B)]; as SELF on eps_c, rows r < fbs read
+//         seed[r] where SELF reads stock[r]
+//   FULL: eps = [eps_u(B) | eps_c(B)]; out[r] = eps_u[r] + g[r]*(eps_c[r]-eps_u[r])
+//         (g arrives in the gm1 argument; no stock)
+// Every arithmetic step rounds to f16, as the aten f16 chain does (f32 math,
+// one rounding per op): with uniform coefficients the result is bit-identical
+// to that chain, and the roundings keep the compiler from contracting across
+// steps. Stock hazard: a thread reads stock[r][i] before it writes the same
+// element and its other source (eps) is read-only, so the in-place shift
+// needs no second buffer. T = f16x8 (per_b % 8 == 0) or f16 (any per_b);
+// per_bv / nv count T-sized units per row / in the output.
+// ---------------------------------------------------------------------------
+enum RcfgMode { RCFG_SELF = 0, RCFG_INIT = 1, RCFG_FULL = 2 };
+
+// f32 coefficient x f16 value: the product is rounded to f32 and THEN to
+// f16, as aten's vectorized f16 kernels and its CPU kernels do. The empty
+// asm keeps the multiply and the conversion apart: left alone the compiler
+// may pick a mixed-precision multiply that rounds straight to f16, and the
+// two disagree wherever the f32 rounding lands on an f16 tie (measured: the
+// scalar path did, the f16x8 path did not). Sums and differences of two f16
+// values need no such care, f32 holds them closely enough (24 >= 2*11 + 2)
+// for the second rounding to be innocuous.
+__device__ __forceinline__ f16 rcfg_scale(float c, f16 x) {
+  float p = c * (float)x;
+  asm volatile("" : "+v"(p));
+  return (f16)p;
+}
+
+__device__ __forceinline__ f16 rcfg_self1(f16 e, f16 s, float gm1, float dl) {
+  const f16 ds = rcfg_scale(dl, s);
+  const f16 df = (f16)((float)e - (float)ds);
+  const f16 sc = rcfg_scale(gm1, df);
+  return (f16)((float)e + (float)sc);
+}
+
+__device__ __forceinline__ f16 rcfg_full1(f16 u, f16 c, float g) {
+  const f16 df = (f16)((float)c - (float)u);
+  const f16 sc = rcfg_scale(g, df);
+  return (f16)((float)u + (float)sc);
+}
+
+__device__ __forceinline__ f16 rcfg_self(f16 e, f16 s, float gm1, float dl) {
+  return rcfg_self1(e, s, gm1, dl);
+}
+__device__ __forceinline__ f16x8 rcfg_self(f16x8 e, f16x8 s, float gm1,
+                                           float dl) {
+  f16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = rcfg_self1(e[j], s[j], gm1, dl);
+  return o;
+}
+__device__ __forceinline__ f16 rcfg_full(f16 u, f16 c, float g) {
+  return rcfg_full1(u, c, g);
+}
+__device__ __forceinline__ f16x8 rcfg_full(f16x8 u, f16x8 c, float g) {
+  f16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = rcfg_full1(u[j], c[j], g);
+  return o;
+}
+
+template <int MODE, typename T>
+__global__ void rcfg_apply_kernel(const T* __restrict__ eps, T* stock,
+                                  const float* __restrict__ gm1,
+                                  const float* __restrict__ delta,
+                                  T* __restrict__ out, long B, long fbs,
+                                  long per_bv, long nv) {
+  for (long i = blockIdx.x * blockDim.x + threadIdx.x; i < nv;
+       i += gridDim.x * blockDim.x) {
+    const long r = i / per_bv;
+    if (MODE == RCFG_FULL) {
+      out[i] = rcfg_full(eps[i], eps[B * per_bv + i], gm1[r]);
+    } else {
+      // conditional rows start after the seed rows in INIT
+      const T* eps_c = MODE == RCFG_INIT ? eps + fbs * per_bv : eps;
+      const T e = eps_c[i];
+      const bool first = r < fbs;
+      const T s = (MODE == RCFG_INIT && first) ? eps[i] : stock[i];
+      out[i] = rcfg_self(e, s, gm1[r], delta[r]);
+      stock[i] = first ? e : eps_c[i - fbs * per_bv];
+    }
+  }
+}
+
+template <typename T>
+static void rcfg_apply_launch(int mode, const T* eps, T* stock,
+                              const float* gm1, const float* delta, T* out,
+                              long B, long fbs, long per_bv, hipStream_t s) {
+  const long nv = B * per_bv;
+  int blocks = (int)min((long)EW_MAX_BLOCKS, (nv + EW_BLOCK - 1) / EW_BLOCK);
+  if (blocks < 1) return;
+#define RCFG_LAUNCH(M)                                                       \
+  hipLaunchKernelGGL((rcfg_apply_kernel<M, T>), dim3(blocks), dim3(EW_BLOCK), \
+                     0, s, eps, stock, gm1, delta, out, B, fbs, per_bv, nv)
+  if (mode == RCFG_SELF) RCFG_LAUNCH(RCFG_SELF);
+  else if (mode == RCFG_INIT) RCFG_LAUNCH(RCFG_INIT);
+  else RCFG_LAUNCH(RCFG_FULL);
+#undef RCFG_LAUNCH
+}
+
+// vec != 0: per_b % 8 == 0 and every pointer 16-byte aligned (caller checks)
+extern "C" void airtc_rcfg_apply(int mode, const uint16_t* eps,
+                                 uint16_t* stock, const float* gm1,
+                                 const float* delta, uint16_t* out, long B,
+                                 long fbs, long per_b, int vec,
+                                 hipStream_t s) {
+  if (vec)
+    rcfg_apply_launch(mode, reinterpret_cast<const f16x8*>(eps),
+                      reinterpret_cast<f16x8*>(stock), gm1, delta,
+                      reinterpret_cast<f16x8*>(out), B, fbs, per_b / 8, s);
+  else
+    rcfg_apply_launch(mode, reinterpret_cast<const f16*>(eps),
+                      reinterpret_cast<f16*>(stock), gm1, delta,
+                      reinterpret_cast<f16*>(out), B, fbs, per_b, s);
+}
+
+// ---------------------------------------------------------------------------
 // fit_resize_u8: any-resolution ingest. One launch crops a source window
 // (y0, x0, ch, cw) out of a u8 RGB NHWC frame, resizes it with the separable
 // antialiased triangle filter (the filter of F.interpolate(mode="bilinear",

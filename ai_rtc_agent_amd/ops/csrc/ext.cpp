@@ -612,6 +612,58 @@ torch::Tensor sched_blend(torch::Tensor xt, torch::Tensor eps,
   return out;
 }
 
+// residual-CFG step (elementwise.hip): one launch, per-row f32 coefficients.
+// mode 0 self / 1 initialize: coef = g-1 per row, stock is read and shifted
+// in place; mode 2 full: coef = g per row, no stock.
+torch::Tensor rcfg_apply(int64_t mode, torch::Tensor eps, torch::Tensor coef,
+                         c10::optional<torch::Tensor> delta,
+                         c10::optional<torch::Tensor> stock, int64_t fbs) {
+  CHECK_IN(eps);
+  CHECK_IN(coef);
+  TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0 (self), 1 (initialize) or 2 (full)");
+  TORCH_CHECK(eps.dtype() == torch::kHalf && coef.dtype() == torch::kFloat);
+  TORCH_CHECK(eps.dim() >= 1 && fbs >= 1);
+  const long B = coef.numel();
+  const long rows_in = mode == 0 ? B : (mode == 1 ? B + fbs : 2 * B);
+  TORCH_CHECK(B >= 1 && eps.size(0) == rows_in, "eps has ", eps.size(0),
+              " rows, mode ", mode, " with ", B, " coefficient rows needs ",
+              rows_in);
+  TORCH_CHECK(fbs <= B && B % fbs == 0, "fbs must divide the row count");
+  const long per_b = eps.numel() / rows_in;
+  auto shape = eps.sizes().vec();
+  shape[0] = B;
+  auto out = torch::empty(shape, eps.options());
+  auto overlap = [](const torch::Tensor& a, const torch::Tensor& b) {
+    const char* a0 = static_cast<const char*>(a.data_ptr());
+    const char* b0 = static_cast<const char*>(b.data_ptr());
+    return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
+  };
+  TORCH_CHECK(!overlap(out, eps), "out must not alias eps");
+  const float* dp = nullptr;
+  uint16_t* sp = nullptr;
+  bool vec = per_b % 8 == 0 && aligned16(eps.data_ptr()) &&
+             aligned16(out.data_ptr());
+  if (mode != 2) {
+    TORCH_CHECK(delta.has_value() && stock.has_value(),
+                "self/initialize need delta and stock");
+    CHECK_IN((*delta));
+    CHECK_IN((*stock));
+    TORCH_CHECK(delta->dtype() == torch::kFloat && delta->numel() == B,
+                "delta must be f32 (B,)");
+    TORCH_CHECK(stock->dtype() == torch::kHalf && stock->sizes() == out.sizes(),
+                "stock must be f16 with the output's shape");
+    TORCH_CHECK(!overlap(*stock, eps), "stock must not alias eps");
+    TORCH_CHECK(!overlap(out, *stock), "out must not alias stock");
+    dp = delta->data_ptr<float>();
+    sp = h_ptr_mut(*stock);
+    vec = vec && aligned16(sp);
+  }
+  if (out.numel() == 0) return out;
+  airtc_rcfg_apply((int)mode, h_ptr(eps), sp, coef.data_ptr<float>(), dp,
+                   h_ptr_mut(out), B, fbs, per_b, vec ? 1 : 0, cur_stream());
+  return out;
+}
+
 // fp8 conv: MX-scaled MFMA path (conv2d_fp8.hip). Same surface as conv2d
 // but weights are pre-quantized e4m3 bytes + per-OC dequant scales, and the
 // activation scale rides along as a scalar.
@@ -793,6 +845,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused q(x_t|x0) sample: a*x0 + b*noise (per-batch-row coeffs)");
   m.def("sched_blend", &sched_blend,
         "fused LCM step: c_out*(x_t - b*eps)/a + c_skip*x_t");
+  m.def("rcfg_apply", &rcfg_apply,
+        "residual-CFG step, per-row f32 coefficients; shifts stock in place");
   m.def("preprocess_u8", &preprocess_u8);
   m.def("postprocess_u8", &postprocess_u8);
   m.def("fit_resize_u8", &fit_resize_u8,

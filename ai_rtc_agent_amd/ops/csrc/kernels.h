@@ -48,6 +48,14 @@ void airtc_sched_blend(const uint16_t* xt, const uint16_t* eps,
                        const float* a, const float* bt, const float* c_out,
                        const float* c_skip, uint16_t* out, long per_b, long n,
                        hipStream_t s);
+// residual-CFG step in one launch, per-row f32 coefficients of B entries
+// (B = output rows). mode 0 self: eps (B), stock (B) read then shifted in
+// place; 1 initialize: eps = [seed(fbs) | cond(B)]; 2 full: eps =
+// [uncond(B) | cond(B)], gm1 holds g, stock/delta unused (may be null).
+// vec != 0 selects the 16-byte path: per_b % 8 == 0, pointers 16-B aligned.
+void airtc_rcfg_apply(int mode, const uint16_t* eps, uint16_t* stock,
+                      const float* gm1, const float* delta, uint16_t* out,
+                      long B, long fbs, long per_b, int vec, hipStream_t s);
 
 // norms ---------------------------------------------------------------------
 // GroupNorm partial statistics, the one layout every producer and consumer

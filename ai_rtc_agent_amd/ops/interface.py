@@ -68,6 +68,12 @@ def _use_hip(x: torch.Tensor) -> bool:
     return True
 
 
+def uses_hip(x: torch.Tensor) -> bool:
+    """Would an op on this tensor run its HIP kernel (rather than the torch
+    reference: CPU, non-f16, AIRTC_FORCE_EAGER=1)?"""
+    return _use_hip(x)
+
+
 def _cached(t: torch.Tensor, key: str, build):
     c = getattr(t, key, None)
     if c is None:
@@ -613,6 +619,99 @@ def sched_blend(x_t: torch.Tensor, eps: torch.Tensor, a32: torch.Tensor,
     x0 = (x_t.float() - b * eps.float()) / a
     y = c_out32.view(sh) * x0 + c_skip32.view(sh) * x_t.float()
     return y.to(x_t.dtype)
+
+
+RCFG_MODES = ("self", "initialize", "full")
+
+
+def _rcfg_chain(mode: str, eps: torch.Tensor, stock, fbs: int, gm1: float,
+                delta: float, g: float) -> torch.Tensor:
+    """The torch chain of ResidualCFG's scalar path, stock shift included."""
+    if mode == "full":
+        half = eps.shape[0] // 2
+        eps_u, eps_c = eps[:half], eps[half:]
+        return eps_u + g * (eps_c - eps_u)
+    eps_c = eps
+    if mode == "initialize":
+        seed, eps_c = eps[:fbs], eps[fbs:]
+        stock[:fbs].copy_(seed)
+    out = eps_c + gm1 * (eps_c - delta * stock)
+    stock.copy_(torch.cat([eps_c[:fbs], eps_c[:-fbs]], dim=0))
+    return out
+
+
+def rcfg_apply(mode: str, eps: torch.Tensor, fbs: int, *,
+               gm1: torch.Tensor | None = None,
+               delta: torch.Tensor | None = None,
+               stock: torch.Tensor | None = None,
+               g: torch.Tensor | None = None) -> torch.Tensor:
+    """Residual-CFG step with per-row f32 coefficients (B,), B = output rows.
+
+    self:       out[r] = eps[r] + gm1[r]*(eps[r] - delta[r]*stock[r]), and
+                `stock` shifts in place: rows < fbs take eps[r], the others
+                eps[r - fbs]
+    initialize: eps = [seed(fbs) | cond(B)]; as self on the cond rows, rows
+                < fbs read seed[r] where self reads stock[r]
+    full:       eps = [uncond(B) | cond(B)]; out[r] = uncond[r] +
+                g[r]*(cond[r] - uncond[r]); no stock
+
+    On the GPU this is one HIP launch (f16) that rounds after every
+    arithmetic step, bit-identical to the f16 torch chain. Elsewhere it IS
+    that chain: whole-batch when the coefficients are uniform, row by row
+    when they differ."""
+    if mode not in RCFG_MODES:
+        raise ValueError(f"mode must be one of {RCFG_MODES}, got {mode!r}")
+    full = mode == "full"
+    coef = g if full else gm1
+    if coef is None or (not full and (delta is None or stock is None)):
+        raise ValueError(
+            "rcfg_apply: full needs g; self/initialize need gm1, delta, stock")
+    if _use_hip(eps):
+        ext = _require_ext()
+        return ext.rcfg_apply(RCFG_MODES.index(mode), eps.contiguous(), coef,
+                              None if full else delta,
+                              None if full else stock, fbs)
+    B = coef.numel()
+    if eps.is_cuda:
+        # eager on the device (f32 engine, AIRTC_FORCE_EAGER=1): reading the
+        # coefficients back would sync and cannot be captured. Broadcast
+        # them instead, f32 math with a rounding to eps.dtype per step —
+        # the kernel's arithmetic, op for op.
+        sh = (-1, *([1] * (eps.dim() - 1)))
+        dt = eps.dtype
+        c32 = coef.view(sh)
+        if full:
+            eps_u, eps_c = eps[:B].float(), eps[B:].float()
+            df = (eps_c - eps_u).to(dt).float()
+            return (eps_u + (c32 * df).to(dt).float()).to(dt)
+        eps_c = eps[eps.shape[0] - B:]
+        if mode == "initialize":
+            stock[:fbs].copy_(eps[:fbs])
+        e = eps_c.float()
+        df = (e - (delta.view(sh) * stock.float()).to(dt).float()).to(dt).float()
+        out = (e + (c32 * df).to(dt).float()).to(dt)
+        stock.copy_(torch.cat([eps_c[:fbs], eps_c[:-fbs]], dim=0))
+        return out
+    cl = coef.tolist()
+    dl = [0.0] * B if full else delta.tolist()
+    if all(c == cl[0] for c in cl) and all(d == dl[0] for d in dl):
+        return _rcfg_chain(mode, eps, stock, fbs, cl[0], dl[0], cl[0])
+    extra = eps.shape[0] - B  # seed rows (initialize) / uncond rows (full)
+    out = torch.empty((B, *eps.shape[1:]), dtype=eps.dtype, device=eps.device)
+    new_stock = None if full else torch.empty_like(stock)
+    for r in range(B):
+        if full:
+            out[r] = _rcfg_chain(mode, eps[r::B], None, 1, 0.0, 0.0, cl[r])[0]
+            continue
+        # one-row chain: row r's "stock" is the seed for the first fbs rows
+        # of initialize; its shifted stock is filled in below
+        s = eps[r] if (mode == "initialize" and r < fbs) else stock[r]
+        e = eps[extra + r]
+        out[r] = e + cl[r] * (e - dl[r] * s)
+        new_stock[r] = e if r < fbs else eps[extra + r - fbs]
+    if not full:
+        stock.copy_(new_stock)
+    return out
 
 
 def upsample_nearest2x_nhwc(x: torch.Tensor) -> torch.Tensor:

@@ -36,11 +36,19 @@ class SlotProxy:
         # returns an awaitable; VideoStreamTrack awaits it
         return self._owner.submit(self.slot, frame)
 
+    # the session's own controls: every update names this proxy's slot, so
+    # it rewrites that slot's rows of the shared engine and nobody else's
     def update_prompt(self, prompt: str) -> None:
-        self._owner.base.update_prompt(prompt)
+        self._owner.base.update_prompt(prompt, slot=self.slot)
+
+    def update_negative_prompt(self, prompt: str) -> None:
+        self._owner.base.update_negative_prompt(prompt, slot=self.slot)
+
+    def update_guidance(self, guidance_scale=None, delta=None) -> None:
+        self._owner.base.update_guidance(guidance_scale, delta, slot=self.slot)
 
     def update_t_index_list(self, t: list) -> None:
-        self._owner.base.update_t_index_list(t)
+        self._owner.base.update_t_index_list(t, slot=self.slot)
 
     def stats(self) -> dict:
         return self._owner.stats()
@@ -66,8 +74,16 @@ class BatchedPipeline:
     def cfg(self):
         return self.base.cfg
 
+    # the broadcast path: replica-wide updates (every slot), which also move
+    # the defaults a re-acquired slot is reset to
     def update_prompt(self, prompt: str) -> None:
         self.base.update_prompt(prompt)
+
+    def update_negative_prompt(self, prompt: str) -> None:
+        self.base.update_negative_prompt(prompt)
+
+    def update_guidance(self, guidance_scale=None, delta=None) -> None:
+        self.base.update_guidance(guidance_scale, delta)
 
     def update_t_index_list(self, t: list) -> None:
         self.base.update_t_index_list(t)
@@ -80,6 +96,10 @@ class BatchedPipeline:
             if not self._active[i]:
                 self._active[i] = True
                 self._sessions[stream_id] = i
+                # nothing of the previous tenant (in-flight latents, RCFG
+                # stock rows, its controls) may reach the new session
+                if hasattr(self.base, "reset_slot"):
+                    self.base.reset_slot(i)
                 if self._task is None or self._task.done():
                     self._task = asyncio.ensure_future(self._run())
                 return SlotProxy(self, i)
@@ -166,11 +186,15 @@ class BatchedPipeline:
         per_slot = []
         for i in range(self.slots):
             lat = sorted(self._lat_ms[i])
-            per_slot.append({
+            entry = {
                 "active": self._active[i],
                 "p50_ms": round(lat[len(lat) // 2], 2) if lat else None,
                 "frames": len(lat),
-            })
+            }
+            if hasattr(self.base, "slot_controls"):
+                # prompt, negative_prompt, guidance_scale, delta, t_index_list
+                entry.update(self.base.slot_controls(i))
+            per_slot.append(entry)
         base = self.base.stats() if hasattr(self.base, "stats") else {}
         return {**base, "batched_slots": self.slots,
                 "active_streams": self.n_active, "per_stream": per_slot}

@@ -220,14 +220,23 @@ class WorkerFrontend:
             body = await request.read()
             import aiohttp
 
+            statuses = []
             for rank in range(self.n):
                 try:
                     async with self._session().post(
                             self._url(rank, "/config"), data=body,
                             headers={"Content-Type": "application/json"}) as r:
                         await r.read()
+                        statuses.append(r.status)
                 except aiohttp.ClientError:
                     logger.warning("config broadcast to worker %d failed", rank)
+            # the workers' verdicts reach the client: a malformed value is
+            # 400 on every worker; a "stream_id" is known to its own worker
+            # only, so it is unknown (404) when every worker says so
+            if 400 in statuses:
+                return web.json_response({"error": "malformed config"}, status=400)
+            if statuses and all(s == 404 for s in statuses):
+                return web.json_response({"error": "unknown stream_id"}, status=404)
             return web.json_response({"status": "ok", "workers": self.n})
 
         async def health(request):

@@ -2,7 +2,8 @@
 
 Parity with reference lib/pipeline.py (L3 of SURVEY.md §1): owns the engine,
 exposes __call__(frame) -> frame plus the runtime update surface
-(update_prompt / update_t_index_list, reference lib/pipeline.py:44-48).
+(update_prompt / update_t_index_list, reference lib/pipeline.py:44-48;
+plus negative prompt and guidance, each addressable per serving slot).
 Pre/post-processing live inside the engine (fused HIP kernels) rather than
 as CV-CUDA calls (reference lib/pipeline.py:50-74).
 
@@ -52,11 +53,28 @@ class StreamDiffusionPipeline:
         self.engine.sync_output()
         return out
 
-    def update_prompt(self, prompt: str) -> None:
-        self.engine.update_prompt(prompt)
+    # runtime updates: slot=None is the whole replica, slot=i one session of
+    # a batched replica (engine/engine.py)
+    def update_prompt(self, prompt: str, slot: Optional[int] = None) -> None:
+        self.engine.update_prompt(prompt, slot=slot)
 
-    def update_t_index_list(self, t_index_list: Sequence[int]) -> None:
-        self.engine.update_t_index_list(list(t_index_list))
+    def update_negative_prompt(self, prompt: str, slot: Optional[int] = None) -> None:
+        self.engine.update_negative_prompt(prompt, slot=slot)
+
+    def update_guidance(self, guidance_scale: Optional[float] = None,
+                        delta: Optional[float] = None,
+                        slot: Optional[int] = None) -> None:
+        self.engine.update_guidance(guidance_scale, delta, slot=slot)
+
+    def update_t_index_list(self, t_index_list: Sequence[int],
+                            slot: Optional[int] = None) -> None:
+        self.engine.update_t_index_list(list(t_index_list), slot=slot)
+
+    def reset_slot(self, slot: int) -> None:
+        self.engine.reset_slot(slot)
+
+    def slot_controls(self, slot: int) -> dict:
+        return self.engine.slot_controls(slot)
 
     def stats(self) -> dict:
         return self.engine.stats()
