@@ -350,7 +350,8 @@ class StreamDiffusionEngine:
                     if hasattr(m, attr):
                         delattr(m, attr)
                 for t in list(m.parameters(recurse=False)):
-                    for attr in ("_airtc_wperm", "_airtc_b32", "_airtc_g32", "_airtc_w16", "_airtc_wpad32", "_airtc_wfp8", "_airtc_wdq"):
+                    for attr in ("_airtc_wperm", "_airtc_b32", "_airtc_g32", "_airtc_w16", "_airtc_wpad32", "_airtc_wfp8", "_airtc_wdq",
+                                 "_airtc_wtail", "_airtc_btail", "_airtc_wtiny"):
                         if hasattr(t, attr):
                             delattr(t, attr)
         from ..parallel.collectives import broadcast_engine_weights

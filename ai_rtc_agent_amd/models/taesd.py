@@ -107,13 +107,16 @@ class TAESDDecoder(nn.Module):
         h = self.conv_in(z, act=ops.ACT_RELU)
         for b in self.stage1:
             h = b(h)
-        h = self.up1(ops.upsample_nearest2x_nhwc(h))
+        # nearest-2x in front of up1/up2/up3: with AIRTC_CONV_UP=1 a shift in
+        # the conv's A-load address on the f16 HIP path (ops.conv2d_nhwc
+        # upsample2x=), else the separate upsample kernel
+        h = self.up1(h, upsample2x=True)
         for b in self.stage2:
             h = b(h)
-        h = self.up2(ops.upsample_nearest2x_nhwc(h))
+        h = self.up2(h, upsample2x=True)
         for b in self.stage3:
             h = b(h)
-        h = self.up3(ops.upsample_nearest2x_nhwc(h))
+        h = self.up3(h, upsample2x=True)
         h = self.stage4(h)
         return self.conv_out(h)
 

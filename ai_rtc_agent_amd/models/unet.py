@@ -157,9 +157,14 @@ class Conv2d(nn.Module):
         in_affine: torch.Tensor | None = None,
         in_act: int = 0,
         stats_groups: int | None = None,
+        tail: tuple | None = None,
+        upsample2x: bool = False,
     ) -> torch.Tensor:
         # stats_groups: group count of the GroupNorm that reads this output
         # directly (ops.conv2d_nhwc) — the f16 split-K path only
+        # tail / upsample2x: see ops.conv2d_nhwc; the fp8 conv knows
+        # neither, so callers keep tails off it and the upsample is
+        # materialised in front of it
         act_r = act if act is not None else (ops.ACT_SILU if fuse_silu else ops.ACT_NONE)
         a_scale = None
         if x.dtype == torch.uint8:
@@ -172,6 +177,9 @@ class Conv2d(nn.Module):
         elif self._fp8_in_scale is not None and not self._fp8_calibrate:
             a_scale = self._fp8_in_scale  # chain head: inline encode
         if a_scale is not None:
+            assert tail is None, "the fp8 conv takes no pointwise tail"
+            if upsample2x:
+                x = ops.upsample_nearest2x_nhwc(x)
             y = ops.conv2d_fp8_nhwc(
                 x, self.weight, a_scale, self.bias, self.stride, self.padding,
                 act=act_r, residual=residual, channel_bias=channel_bias,
@@ -184,6 +192,7 @@ class Conv2d(nn.Module):
             x, self.weight, self.bias, self.stride, self.padding, fuse_silu,
             act=act, residual=residual, channel_bias=channel_bias,
             in_affine=in_affine, in_act=in_act, stats_groups=stats_groups,
+            tail=tail, upsample2x=upsample2x,
         )
         if self._fp8_calibrate:
             self._fp8_in_amax = max(self._fp8_in_amax,
@@ -432,9 +441,21 @@ class ResnetBlock(nn.Module):
                               in_affine=self.norm2.coeffs(h), in_act=ops.ACT_SILU)
         h = self.conv1(self.norm1(x), channel_bias=temb_b,
                        stats_groups=self.norm2.groups)
+        hn = self.norm2(h)
+        if (self.shortcut is not None and ops.uses_hip(x)
+                and ops.uses_hip(hn) and not self.norm2._fp8_calibrate
+                and self.conv2._fp8_in_scale is None):
+            # the 1x1 shortcut rides in conv2's K loop as a second segment
+            # (ops.conv2d_nhwc tail=): no shortcut conv, no finalize of its
+            # own, no f16 rounding of the skip. f16 HIP path only — the fp8
+            # tier's norm2 hands conv2 e4m3 codes and keeps the pair, also
+            # while it calibrates on f16 frames (the scales are then
+            # measured on the activations the frozen tier will see).
+            return self.conv2(hn, stats_groups=next_groups,
+                              tail=(x, self.shortcut.weight,
+                                    self.shortcut.bias))
         skip = self.shortcut(x) if self.shortcut is not None else x
-        return self.conv2(self.norm2(h), residual=skip,
-                          stats_groups=next_groups)
+        return self.conv2(hn, residual=skip, stats_groups=next_groups)
 
 
 def fp8_eligible_norms(unet: nn.Module) -> list:
@@ -467,7 +488,9 @@ class Upsample(nn.Module):
         self.conv = Conv2d(channels, channels, 3)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self.conv(ops.upsample_nearest2x_nhwc(x))
+        # with AIRTC_CONV_UP=1 the nearest-2x is a shift in the conv's A-load
+        # address on the f16 HIP path (ops.conv2d_nhwc upsample2x=)
+        return self.conv(x, upsample2x=True)
 
 
 class UNet2DCondition(nn.Module):

@@ -26,7 +26,23 @@
 // Geometry A (large M): BM=128 BN=64, 4 waves (2x2), wave=64x32, 8 MFMA/step
 // Geometry B (small M): BM=64  BN=64, 4 waves (2x2), wave=32x32, 4 MFMA/step
 // Both take split-K over blockIdx.z; the rest of the file is the split-K
-// finalize kernels and the small-IC / direct kernels for IC % 32 != 0.
+// finalize kernels and the tiny-IC / small-IC / direct kernels for
+// IC % 32 != 0.
+//
+// Operands read where they lie (no kernel whose only job is to move them):
+//  - SECOND K SEGMENT: an optional second A source x2 (B, HO, WO, IC2), read
+//    as a 1x1 stride-1 tap at the output pixel by the K-tiles past R*S*IC
+//    against one packed (OC, R*S*IC + IC2) weight — a resnet's 1x1 shortcut
+//    inside conv2's K loop. The source is picked per K-tile (block-uniform)
+//    in load_tile; split-K and the finalize only see a longer K.
+//  - NEAREST-2X IN THE A-LOAD: bounds against the upsampled extents, address
+//    (hi>>1, wi>>1) on the half-size source. Bit-identical to upsample +
+//    conv.
+//    Both are compile-time modes of conv2d_mfma_kernel (third template
+//    parameter): as runtime arguments they cost ~5 % on every plain conv.
+//  - TINY IC (IC <= 4, the 4-channel conv_in layers): conv2d_tinyic_kernel,
+//    lanes along OC, weights in registers, pixels as LDS broadcasts,
+//    coalesced 128 B stores, no scratch.
 
 #include <stdlib.h>
 
@@ -49,6 +65,12 @@ __device__ __forceinline__ KPos kpos_at(int k0, int IC, int S) {
 // kernel and a full activation HBM round-trip disappear. Padding lanes
 // stay zero (ok-gated): the transform models act(gn(x)) of the unfused
 // pipeline, which the conv then zero-pads.
+// UP (0/1, compile time): the conv reads a nearest-2x upsampled view of its
+// source. H, W are the extents the conv sees (bounds check); the source is
+// (H>>1, W>>1) and the tap's address is (hi>>1, wi>>1) — a shift in the
+// address, no arithmetic on the data, same values in the same K order as a
+// materialised upsample.
+template <int UP>
 __device__ __forceinline__ f16x8 load_a(const f16* xb, int ho_s, int wo_s,
                                         int r, int s, int pad, int H, int W,
                                         int IC, int ic, const float* aff,
@@ -56,8 +78,9 @@ __device__ __forceinline__ f16x8 load_a(const f16* xb, int ho_s, int wo_s,
   const int hi = ho_s + r - pad;
   const int wi = wo_s + s - pad;
   const bool ok = (unsigned)hi < (unsigned)H && (unsigned)wi < (unsigned)W;
-  const int hc = ok ? hi : 0, wc = ok ? wi : 0;
-  f16x8 v = *reinterpret_cast<const f16x8*>(&xb[((long)hc * W + wc) * IC + ic]);
+  const int hc = ok ? hi >> UP : 0, wc = ok ? wi >> UP : 0;
+  f16x8 v = *reinterpret_cast<const f16x8*>(
+      &xb[((long)hc * (W >> UP) + wc) * IC + ic]);
   if (!ok) {
     v = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
   } else if (aff) {
@@ -89,15 +112,32 @@ __device__ __forceinline__ f16 epilogue(float acc, const float* bias,
 // splitk = number of K splits (>= 1) carried in blockIdx.z next to the
 // batch; splitk > 1: partials go to ws (f32), the finalize pass reduces.
 // Schedule: register-staged, single LDS buffer, two barriers per K-step.
+// MODE selects how the A operand is addressed. It is a template parameter
+// and not a kernel argument because the runtime form (a variable shift in
+// load_a, a branch in load_tile) measured ~5 % on EVERY conv of the frame;
+// MODE 0 compiles to the plain kernel.
+//  CONV_PLAIN: x only.
+//  CONV_TAIL:  x2/IC2 is a second K segment, a (B, HO, WO, IC2) tensor read
+//    as a 1x1 stride-1 unpadded tap at the output pixel. w rows are
+//    [R*S*IC | IC2] long (K = R*S*IC + IC2) and K-tiles past R*S*IC stage
+//    their A chunk from x2 — the choice is per K-tile, block-uniform, made
+//    in load_tile. Needs stride == 1 and IC2 % BK == 0 (host-checked).
+//    in_aff applies to segment 0 only.
+//  CONV_UP:    nearest-2x source addressing of x (load_a<1>): x is
+//    (B, H/2, W/2, IC), H and W stay the extents the conv sees.
 // ---------------------------------------------------------------------------
-template <int MFRAG, int BK>
+enum { CONV_PLAIN = 0, CONV_TAIL = 1, CONV_UP = 2 };
+
+template <int MFRAG, int BK, int MODE>
 __global__ __launch_bounds__(256) void conv2d_mfma_kernel(
     const f16* __restrict__ x, const f16* __restrict__ w,
     const float* __restrict__ bias, const f16* __restrict__ cbias,
     const f16* __restrict__ residual, f16* __restrict__ out,
     float* __restrict__ ws, int H, int W, int IC, int HO, int WO, int OC,
     int R, int S, int stride, int pad, int act, int K, int splitk,
-    const float* __restrict__ in_aff, int in_act) {
+    const float* __restrict__ in_aff, int in_act,
+    const f16* __restrict__ x2, int IC2) {
+  constexpr int UP = MODE == CONV_UP ? 1 : 0;
   constexpr int BM = MFRAG * 32;              // 128 or 64
   constexpr int NFRAG = BN / 32;              // N-fragments per wave
   constexpr int KPITCH = BK + 8;              // +16B row pad (guide G4)
@@ -116,8 +156,10 @@ __global__ __launch_bounds__(256) void conv2d_mfma_kernel(
   const int n0 = nt * BN;
   const int b = blockIdx.z / splitk;
   const int split = blockIdx.z - b * splitk;
-  const f16* xb = x + (long)b * H * W * IC;
+  const f16* xb = x + (long)b * (H >> UP) * (W >> UP) * IC;
   const float* affb = in_aff ? in_aff + (long)b * IC * 2 : nullptr;
+  const int K1 = K - IC2;                     // end of the conv segment
+  const f16* x2b = x2 + (long)b * M * IC2;    // used only when IC2 > 0
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -163,11 +205,27 @@ __global__ __launch_bounds__(256) void conv2d_mfma_kernel(
   // staging helpers
   f16x8 regA[ALOADS], regB[BLOADS];
   auto load_tile = [&](int kt) {
-    KPos p = kpos_at(kt * BK, IC, S);
+    const int k0 = kt * BK;
+    if (MODE != CONV_TAIL || k0 < K1) {
+      KPos p = kpos_at(k0, IC, S);
 #pragma unroll
-    for (int i = 0; i < ALOADS; ++i)
-      regA[i] = load_a(xb, a_ho[i], a_wo[i], p.r, p.s, pad, H, W, IC,
-                       p.ic0 + a_k8[i], affb, in_act);
+      for (int i = 0; i < ALOADS; ++i)
+        regA[i] = load_a<UP>(xb, a_ho[i], a_wo[i], p.r, p.s, pad, H, W, IC,
+                             p.ic0 + a_k8[i], affb, in_act);
+    } else {
+      // pointwise tail: stride 1, so a_ho/a_wo are the output pixel itself
+      const f16* t = x2b + (k0 - K1);
+#pragma unroll
+      for (int i = 0; i < ALOADS; ++i) {
+        // the pixel offset is loop-invariant; recomputing it per tail tile
+        // from a_ho/a_wo (opaque to the optimiser) keeps it from being
+        // hoisted into ALOADS extra live registers across the main K loop
+        int ho = a_ho[i];
+        asm volatile("" : "+v"(ho));
+        regA[i] = *reinterpret_cast<const f16x8*>(
+            &t[(ho * WO + a_wo[i]) * IC2 + a_k8[i]]);
+      }
+    }
 #pragma unroll
     for (int i = 0; i < BLOADS; ++i)
       regB[i] = *reinterpret_cast<const f16x8*>(wrow[i] + kt * BK);
@@ -376,7 +434,8 @@ __global__ __launch_bounds__(256) void conv_splitk_finalize_v4(
 }
 
 // ---------------------------------------------------------------------------
-// Small-IC conv (conv_in with IC=3/4): one thread per output PIXEL computing
+// Small-IC conv (ragged IC < 32; the 3/4-channel conv_in layers now take
+// conv2d_tinyic_kernel below): one thread per output PIXEL computing
 // a 64-wide OC tile in registers, weights staged once in LDS (uniform k ->
 // broadcast reads). The one-thread-per-output direct kernel re-reads each
 // input pixel OC times (measured 169us for TAESD conv_in @512²); this reads
@@ -435,6 +494,79 @@ __global__ __launch_bounds__(256) void conv2d_smallic_kernel(
     for (int o = 0; o < noc; ++o)
       out[obase + o] = epilogue(acc[o], bias, cbias, cb_off, residual,
                                 obase + o, oc0 + o, act);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Tiny-IC conv (the 4- and 3-channel conv_in layers, K = R*S*IC <= 36):
+// lanes along OC. A wave owns one 64-wide OC tile: each lane keeps its
+// output channel's K weights in registers (read coalesced from a (TK, OC)
+// f32 pack built once per weight, rows past K zero) and the block's pixels
+// are staged as zero-padded f32 im2col rows in LDS, read back as wave-uniform
+// broadcasts. Per pixel a wave issues TK FMAs per lane and ONE coalesced
+// 128 B f16 store — against the per-pixel kernel above there are no 64
+// accumulators per thread (no scratch) and no strided 2 B stores, and the
+// grid is pixel chunks x OC tiles (>= 2 blocks per CU at 64²: ppb is sized
+// by the host). Accumulation order is (r, s, c) ascending in f32, as above.
+// ---------------------------------------------------------------------------
+#define TINY_TK 36    // 3x3 x IC<=4
+#define TINY_PPB 64   // max pixels per block
+
+__global__ __launch_bounds__(256) void conv2d_tinyic_kernel(
+    const f16* __restrict__ x, const float* __restrict__ wt,
+    const float* __restrict__ bias, const f16* __restrict__ cbias,
+    const f16* __restrict__ residual, f16* __restrict__ out, int H, int W,
+    int IC, int HO, int WO, int OC, int S, int stride, int pad, int act,
+    int K, long total_pix, int ppb) {
+  __shared__ __attribute__((aligned(16))) float xs[TINY_PPB * TINY_TK];
+  const long pix0 = blockIdx.x * (long)ppb;
+  const int npix = (int)min((long)ppb, total_pix - pix0);
+  const int M = HO * WO;
+  // im2col rows of this block's pixels, zero where padded or past K
+  for (int i = threadIdx.x; i < npix * TINY_TK; i += 256) {
+    const int p = i / TINY_TK, k = i - p * TINY_TK;
+    float v = 0.f;
+    if (k < K) {
+      const long pix = pix0 + p;
+      const long b = pix / M;
+      const int m = (int)(pix - b * M);
+      const int ho = m / WO, wo = m - ho * WO;
+      const int rs = k / IC, c = k - rs * IC;
+      const int r = rs / S, s = rs - r * S;
+      const int hi = ho * stride + r - pad, wi = wo * stride + s - pad;
+      if ((unsigned)hi < (unsigned)H && (unsigned)wi < (unsigned)W)
+        v = (float)x[((b * H + hi) * (long)W + wi) * IC + c];
+    }
+    xs[i] = v;
+  }
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int oc = blockIdx.y * 64 + lane;
+  const bool live = oc < OC;
+  float wr[TINY_TK];
+#pragma unroll
+  for (int k = 0; k < TINY_TK; ++k) wr[k] = live ? wt[(long)k * OC + oc] : 0.f;
+  const float bv = (bias && live) ? bias[oc] : 0.f;
+  __syncthreads();
+  for (int p = wid; p < npix; p += 4) {
+    const f32x4* xr = reinterpret_cast<const f32x4*>(&xs[p * TINY_TK]);
+    float a = 0.f;
+#pragma unroll
+    for (int q = 0; q < TINY_TK / 4; ++q) {
+      const f32x4 xv = xr[q];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) a += xv[j] * wr[q * 4 + j];
+    }
+    if (live) {
+      const long pix = pix0 + p;
+      const long b = pix / M;
+      const long idx = pix * OC + oc;
+      float v = a;
+      if (bias) v += bv;
+      if (cbias) v += (float)cbias[b * OC + oc];
+      if (residual) v += (float)residual[idx];
+      out[idx] = (f16)apply_act(v, act);
+    }
   }
 }
 
@@ -566,9 +698,13 @@ extern "C" int airtc_conv2d_mfma(const uint16_t* x, const uint16_t* w,
                                  int stride, int pad, int act, int path,
                                  const float* in_aff, int in_act,
                                  float* gn_part, int gn_groups,
+                                 const uint16_t* x2, int IC2, int up,
                                  hipStream_t s) {
-  const int K = R * S * IC;
+  // H, W: the extents the conv sees (the upsampled ones when up == 1);
+  // w rows are R*S*IC + IC2 long
+  const int K = R * S * IC + IC2;
   const f16* xp = reinterpret_cast<const f16*>(x);
+  const f16* x2p = reinterpret_cast<const f16*>(x2);
   const f16* wp = reinterpret_cast<const f16*>(w);
   const f16* cb = reinterpret_cast<const f16*>(cbias);
   const f16* res = reinterpret_cast<const f16*>(residual);
@@ -582,18 +718,28 @@ extern "C" int airtc_conv2d_mfma(const uint16_t* x, const uint16_t* w,
   const float* b1 = splitk == 1 ? bias : nullptr;
   const f16* cb1 = splitk == 1 ? cb : nullptr;
   const f16* res1 = splitk == 1 ? res : nullptr;
-  const bool bk64 = (IC % 64 == 0);
-#define CONV_LAUNCH(MF, BKV)                                                  \
-  hipLaunchKernelGGL((conv2d_mfma_kernel<MF, BKV>), grid, dim3(256), 0, s,    \
-                     xp, wp, b1, cb1, res1, op, ws, H, W, IC, HO, WO, OC, R,  \
-                     S, stride, pad, act, K, splitk, in_aff, in_act)
-  if (path > 0) {
-    if (bk64) CONV_LAUNCH(4, 64);
-    else CONV_LAUNCH(4, 32);
-  } else {
-    if (bk64) CONV_LAUNCH(2, 64);
-    else CONV_LAUNCH(2, 32);
-  }
+  // both K segments must be whole K-tiles
+  const bool bk64 = (IC % 64 == 0) && (IC2 % 64 == 0);
+  if (x2p && up) return -1;  // one addressing mode per launch
+#define CONV_LAUNCH(MF, BKV, MD)                                              \
+  hipLaunchKernelGGL((conv2d_mfma_kernel<MF, BKV, MD>), grid, dim3(256), 0,   \
+                     s, xp, wp, b1, cb1, res1, op, ws, H, W, IC, HO, WO, OC,  \
+                     R, S, stride, pad, act, K, splitk, in_aff, in_act, x2p,  \
+                     IC2)
+#define CONV_GEOM(MD)                                                         \
+  do {                                                                        \
+    if (path > 0) {                                                           \
+      if (bk64) CONV_LAUNCH(4, 64, MD);                                       \
+      else CONV_LAUNCH(4, 32, MD);                                            \
+    } else {                                                                  \
+      if (bk64) CONV_LAUNCH(2, 64, MD);                                       \
+      else CONV_LAUNCH(2, 32, MD);                                            \
+    }                                                                         \
+  } while (0)
+  if (x2p) CONV_GEOM(CONV_TAIL);
+  else if (up) CONV_GEOM(CONV_UP);
+  else CONV_GEOM(CONV_PLAIN);
+#undef CONV_GEOM
 #undef CONV_LAUNCH
   if (splitk > 1) {
     // 16 B slab / bias loads and 8 B f16 accesses need these alignments
@@ -629,6 +775,32 @@ extern "C" int airtc_conv2d_mfma(const uint16_t* x, const uint16_t* w,
     }
   }
   return 0;
+}
+
+extern "C" int airtc_conv2d_tinyic_ok(int IC, int R, int S) {
+  return IC <= 4 && R * S * IC <= TINY_TK;
+}
+
+// wt: (TINY_TK, OC) f32, row k = weight column k of the (OC, R*S*IC) GEMM
+// layout, rows past K zero
+extern "C" void airtc_conv2d_tinyic(const uint16_t* x, const float* wt,
+                                    const float* bias, const uint16_t* cbias,
+                                    const uint16_t* residual, uint16_t* out,
+                                    int B, int H, int W, int IC, int HO,
+                                    int WO, int OC, int R, int S, int stride,
+                                    int pad, int act, hipStream_t s) {
+  const long pix = (long)B * HO * WO;
+  const int tiles = ceil_div(OC, 64);
+  // largest pixel chunk that still gives >= 512 blocks (2 per CU), 8..64
+  int ppb = TINY_PPB;
+  while (ppb > 8 && ((pix + ppb - 1) / ppb) * tiles < 512) ppb >>= 1;
+  dim3 grid((uint32_t)((pix + ppb - 1) / ppb), tiles);
+  hipLaunchKernelGGL(conv2d_tinyic_kernel, grid, dim3(256), 0, s,
+                     reinterpret_cast<const f16*>(x), wt, bias,
+                     reinterpret_cast<const f16*>(cbias),
+                     reinterpret_cast<const f16*>(residual),
+                     reinterpret_cast<f16*>(out), H, W, IC, HO, WO, OC, S,
+                     stride, pad, act, R * S * IC, pix, ppb);
 }
 
 extern "C" void airtc_conv2d_direct(const uint16_t* x, const uint16_t* w,

@@ -30,7 +30,9 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // stats_groups > 0 asks the split-K finalize for GroupNorm partials of the
 // output (kernels.h layout); *gn_part stays undefined when the shape takes
-// no finalize pass or the finalize cannot produce them
+// no finalize pass or the finalize cannot produce them.
+// x2: optional second K segment (B, HO, WO, IC2), w_perm then (OC, R*S*IC +
+// IC2); upsample2x: x is read through nearest-2x addressing (MFMA path only)
 torch::Tensor conv2d_impl(torch::Tensor x, torch::Tensor w_perm,
                           c10::optional<torch::Tensor> bias,
                           c10::optional<torch::Tensor> cbias,
@@ -38,11 +40,15 @@ torch::Tensor conv2d_impl(torch::Tensor x, torch::Tensor w_perm,
                           int64_t S, int64_t stride, int64_t pad, int64_t act,
                           c10::optional<torch::Tensor> in_affine,
                           int64_t in_act, int64_t stats_groups,
-                          torch::Tensor* gn_part) {
+                          torch::Tensor* gn_part,
+                          c10::optional<torch::Tensor> x2, bool upsample2x) {
   CHECK_IN(x);
   CHECK_IN(w_perm);
   TORCH_CHECK(x.dtype() == torch::kHalf && w_perm.dtype() == torch::kHalf);
-  const int B = x.size(0), H = x.size(1), W = x.size(2), IC = x.size(3);
+  TORCH_CHECK(x.dim() == 4 && w_perm.dim() == 2);
+  const int up = upsample2x ? 1 : 0;
+  const int B = x.size(0), IC = x.size(3);
+  const int H = (int)x.size(1) << up, W = (int)x.size(2) << up;
   const int OC = w_perm.size(0);
   const int HO = (H + 2 * (int)pad - (int)R) / (int)stride + 1;
   const int WO = (W + 2 * (int)pad - (int)S) / (int)stride + 1;
@@ -73,7 +79,26 @@ torch::Tensor conv2d_impl(torch::Tensor x, torch::Tensor w_perm,
                 "in_affine must be (B, IC, 2) f32");
     aff = in_affine->data_ptr<float>();
   }
+  const uint16_t* x2p = nullptr;
+  int IC2 = 0;
+  if (x2.has_value()) {
+    CHECK_IN((*x2));
+    TORCH_CHECK(x2->dtype() == torch::kHalf && x2->dim() == 4);
+    IC2 = x2->size(3);
+    TORCH_CHECK(x2->size(0) == B && x2->size(1) == HO && x2->size(2) == WO,
+                "x2 must be (B, HO, WO, IC2)");
+    TORCH_CHECK(stride == 1 && IC2 > 0 && IC2 % 32 == 0,
+                "x2 needs stride 1 and IC2 % 32 == 0");
+    // the kernel offsets x2 per batch in 32 bits
+    TORCH_CHECK((long)HO * WO * IC2 < (1L << 31), "x2 too large");
+    x2p = h_ptr(*x2);
+  }
+  TORCH_CHECK(w_perm.size(1) == (long)R * S * IC + IC2,
+              "w_perm must be (OC, R*S*IC + IC2)");
   const int path = airtc_conv2d_splitk_for(B, HO, WO, OC, IC);
+  TORCH_CHECK(path != 0 || (!x2p && !up),
+              "x2 / upsample2x need the MFMA path (IC % 32 == 0)");
+  TORCH_CHECK(!(x2p && up), "x2 and upsample2x exclude each other");
   if (path == 0) {
     airtc_conv2d_direct(h_ptr(x), h_ptr(w_perm), bp, cb, res, h_ptr_mut(out),
                         B, H, W, IC, HO, WO, OC, (int)R, (int)S, (int)stride,
@@ -102,7 +127,7 @@ torch::Tensor conv2d_impl(torch::Tensor x, torch::Tensor w_perm,
   const int wrote = airtc_conv2d_mfma(
       h_ptr(x), h_ptr(w_perm), bp, cb, res, h_ptr_mut(out), wsp, B, H, W, IC,
       HO, WO, OC, (int)R, (int)S, (int)stride, (int)pad, (int)act, path, aff,
-      (int)in_act, gnp, (int)stats_groups, cur_stream());
+      (int)in_act, gnp, (int)stats_groups, x2p, IC2, up, cur_stream());
   // the launcher has the last word: partials it did not write are dropped,
   // and the consumer norm runs its own statistics pass
   if (gnp && !wrote) *gn_part = torch::Tensor();
@@ -114,9 +139,60 @@ torch::Tensor conv2d(torch::Tensor x, torch::Tensor w_perm,
                      c10::optional<torch::Tensor> cbias,
                      c10::optional<torch::Tensor> residual, int64_t R,
                      int64_t S, int64_t stride, int64_t pad, int64_t act,
-                     c10::optional<torch::Tensor> in_affine, int64_t in_act) {
+                     c10::optional<torch::Tensor> in_affine, int64_t in_act,
+                     c10::optional<torch::Tensor> x2, bool upsample2x) {
   return conv2d_impl(x, w_perm, bias, cbias, residual, R, S, stride, pad, act,
-                     in_affine, in_act, 0, nullptr);
+                     in_affine, in_act, 0, nullptr, x2, upsample2x);
+}
+
+// tiny-IC conv (IC <= 4, K <= 36): lanes along OC (conv2d.hip). w_tiny is the
+// (36, OC) f32 pack of the weight.
+torch::Tensor conv2d_tinyic(torch::Tensor x, torch::Tensor w_tiny,
+                            c10::optional<torch::Tensor> bias,
+                            c10::optional<torch::Tensor> cbias,
+                            c10::optional<torch::Tensor> residual, int64_t R,
+                            int64_t S, int64_t stride, int64_t pad,
+                            int64_t act) {
+  CHECK_IN(x);
+  CHECK_IN(w_tiny);
+  TORCH_CHECK(x.dtype() == torch::kHalf && x.dim() == 4);
+  const int B = x.size(0), H = x.size(1), W = x.size(2), IC = x.size(3);
+  TORCH_CHECK(airtc_conv2d_tinyic_ok(IC, (int)R, (int)S),
+              "conv2d_tinyic needs IC <= 4 and R*S*IC <= 36");
+  TORCH_CHECK(w_tiny.dtype() == torch::kFloat && w_tiny.dim() == 2 &&
+                  w_tiny.size(0) == 36,
+              "w_tiny must be (36, OC) f32");
+  TORCH_CHECK(stride >= 1 && pad >= 0);
+  const int OC = w_tiny.size(1);
+  const int HO = (H + 2 * (int)pad - (int)R) / (int)stride + 1;
+  const int WO = (W + 2 * (int)pad - (int)S) / (int)stride + 1;
+  TORCH_CHECK(HO > 0 && WO > 0);
+  auto out = torch::empty({B, HO, WO, OC}, x.options());
+  const float* bp = nullptr;
+  if (bias.has_value()) {
+    CHECK_IN((*bias));
+    TORCH_CHECK(bias->dtype() == torch::kFloat && bias->numel() == OC);
+    bp = bias->data_ptr<float>();
+  }
+  const uint16_t* cb = nullptr;
+  if (cbias.has_value()) {
+    CHECK_IN((*cbias));
+    TORCH_CHECK(cbias->dtype() == torch::kHalf &&
+                cbias->numel() == (long)B * OC);
+    cb = h_ptr(*cbias);
+  }
+  const uint16_t* res = nullptr;
+  if (residual.has_value()) {
+    CHECK_IN((*residual));
+    TORCH_CHECK(residual->dtype() == torch::kHalf);
+    TORCH_CHECK(residual->numel() == out.numel(), "residual shape mismatch");
+    res = h_ptr(*residual);
+  }
+  if (out.numel() == 0) return out;
+  airtc_conv2d_tinyic(h_ptr(x), w_tiny.data_ptr<float>(), bp, cb, res,
+                      h_ptr_mut(out), B, H, W, IC, HO, WO, OC, (int)R, (int)S,
+                      (int)stride, (int)pad, (int)act, cur_stream());
+  return out;
 }
 
 // conv2d + GroupNorm partials for the consumer norm: (out, partials | None)
@@ -127,10 +203,13 @@ pybind11::tuple conv2d_stats(torch::Tensor x, torch::Tensor w_perm,
                              int64_t S, int64_t stride, int64_t pad,
                              int64_t act,
                              c10::optional<torch::Tensor> in_affine,
-                             int64_t in_act, int64_t stats_groups) {
+                             int64_t in_act, int64_t stats_groups,
+                             c10::optional<torch::Tensor> x2,
+                             bool upsample2x) {
   torch::Tensor part;
   auto out = conv2d_impl(x, w_perm, bias, cbias, residual, R, S, stride, pad,
-                         act, in_affine, in_act, stats_groups, &part);
+                         act, in_affine, in_act, stats_groups, &part, x2,
+                         upsample2x);
   if (part.defined()) return pybind11::make_tuple(out, part);
   return pybind11::make_tuple(out, pybind11::none());
 }
@@ -814,7 +893,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("cbias"), pybind11::arg("residual"), pybind11::arg("R"),
         pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"),
         pybind11::arg("act"), pybind11::arg("in_affine") = pybind11::none(),
-        pybind11::arg("in_act") = 0);
+        pybind11::arg("in_act") = 0, pybind11::arg("x2") = pybind11::none(),
+        pybind11::arg("upsample2x") = false);
+  m.def("conv2d_tinyic", &conv2d_tinyic,
+        "tiny-IC conv (IC <= 4, K <= 36), lanes along OC (NHWC)",
+        pybind11::arg("x"), pybind11::arg("w_tiny"), pybind11::arg("bias"),
+        pybind11::arg("cbias"), pybind11::arg("residual"), pybind11::arg("R"),
+        pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"),
+        pybind11::arg("act"));
   m.def("conv2d_stats", &conv2d_stats,
         "conv2d that also returns GroupNorm partials of its output for a "
         "consumer norm with stats_groups groups: (out, partials | None)",
@@ -822,7 +908,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("cbias"), pybind11::arg("residual"), pybind11::arg("R"),
         pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"),
         pybind11::arg("act"), pybind11::arg("in_affine"),
-        pybind11::arg("in_act"), pybind11::arg("stats_groups"));
+        pybind11::arg("in_act"), pybind11::arg("stats_groups"),
+        pybind11::arg("x2") = pybind11::none(),
+        pybind11::arg("upsample2x") = false);
   m.def("group_norm_silu", &group_norm_silu, pybind11::arg("x"),
         pybind11::arg("groups"), pybind11::arg("gamma"), pybind11::arg("beta"),
         pybind11::arg("eps"), pybind11::arg("act"),

@@ -106,7 +106,21 @@ int airtc_conv2d_mfma(const uint16_t* x, const uint16_t* w, const float* bias,
                       int HO, int WO, int OC, int R, int S, int stride,
                       int pad, int act, int path, const float* in_aff,
                       int in_act, float* gn_part, int gn_groups,
-                      hipStream_t s);
+                      const uint16_t* x2, int IC2, int up, hipStream_t s);
+// x2/IC2: optional second K segment (pointwise tail): a (B, HO, WO, IC2)
+// tensor read as a 1x1 stride-1 tap at the output pixel; w rows are then
+// R*S*IC + IC2 long. Needs stride == 1 and IC2 % 32 == 0.
+// up: 1 = x is (B, H/2, W/2, IC) and is read through nearest-2x addressing;
+// H, W stay the extents the conv sees. x2 and up exclude each other (one
+// addressing mode per launch; returns -1 and launches nothing).
+// Tiny-IC conv (IC <= 4, R*S*IC <= 36; airtc_conv2d_tinyic_ok): lanes along
+// OC, wt is the (36, OC) f32 weight pack (row k = GEMM column k, rest zero).
+int airtc_conv2d_tinyic_ok(int IC, int R, int S);
+void airtc_conv2d_tinyic(const uint16_t* x, const float* wt, const float* bias,
+                         const uint16_t* cbias, const uint16_t* residual,
+                         uint16_t* out, int B, int H, int W, int IC, int HO,
+                         int WO, int OC, int R, int S, int stride, int pad,
+                         int act, hipStream_t s);
 // gn_part: optional GroupNorm partials of the OUTPUT for a consumer norm
 // with gn_groups groups (layout above), written by the split-K finalize from
 // the rounded f16 values. Pass it only when airtc_conv2d_stats_nchunk

@@ -86,6 +86,44 @@ def _cached(t: torch.Tensor, key: str, build):
 # conv2d (NHWC activations, OIHW weights)
 # ---------------------------------------------------------------------------
 
+def _switch(name: str, default: str = "1") -> bool:
+    """A/B switch, read per call: NAME=0 is off, NAME=1 on, unset the
+    default."""
+    return os.environ.get(name, default) != "0"
+
+
+def _tiny_pack(weight: torch.Tensor) -> torch.Tensor:
+    """(O,I,R,S) -> the tiny-IC kernel's (36, O) f32 pack: row k is column k
+    of the (O, R*S*I) GEMM layout, rows past R*S*I zero."""
+    O = weight.shape[0]
+    w = weight.detach().permute(0, 2, 3, 1).reshape(O, -1).half().float()
+    out = torch.zeros((36, O), dtype=torch.float32, device=weight.device)
+    out[: w.shape[1]] = w.t()
+    return out.contiguous()
+
+
+def _tail_pack(weight, w_perm, bias, w2, b2):
+    """Packed (O, R*S*I + C2) f16 weight and summed f32 bias of a conv with
+    a pointwise tail, cached on the conv's weight (`_airtc_wtail`,
+    `_airtc_btail`) together with the tensors they were built from."""
+    c = getattr(weight, "_airtc_wtail", None)
+    if c is None or c[0] is not w2:
+        w2p = _cached(w2, "_airtc_wperm",
+                      lambda: w2.detach().permute(0, 2, 3, 1)
+                      .reshape(w2.shape[0], -1).contiguous().half())
+        c = (w2, torch.cat([w_perm, w2p], dim=1).contiguous())
+        weight._airtc_wtail = c
+    cb = getattr(weight, "_airtc_btail", None)
+    if cb is None or cb[0] is not bias or cb[1] is not b2:
+        parts = [b.detach().float() for b in (bias, b2) if b is not None]
+        tot = None
+        if parts:
+            tot = (parts[0] + parts[1] if len(parts) == 2 else parts[0]).contiguous()
+        cb = (bias, b2, tot)
+        weight._airtc_btail = cb
+    return c[1], cb[2]
+
+
 def conv2d_nhwc(
     x: torch.Tensor,
     weight: torch.Tensor,
@@ -99,8 +137,24 @@ def conv2d_nhwc(
     in_affine: torch.Tensor | None = None,
     in_act: int = ACT_NONE,
     stats_groups: int | None = None,
+    tail: tuple | None = None,
+    upsample2x: bool = False,
 ) -> torch.Tensor:
     """x: (B,H,W,C) contiguous; weight: (O,I,R,S) [torch layout]; out (B,H',W',O).
+
+    tail=(x2, w2, b2): adds the pointwise conv W2·x2 (+ b2) to the result
+      before the epilogue — a resnet's 1x1 shortcut. x2 is (B,H',W',C2), w2
+      (O,C2,1,1), b2 (O,) or None. GPU: one GEMM over the longer K
+      (R*S*C + C2) against a packed weight cached on `weight` — the
+      shortcut's conv, its finalize and the f16 rounding of the skip
+      disappear. Folded when stride == 1 and C, C2 are multiples of 32;
+      otherwise, and with AIRTC_CONV_TAIL=0, the shortcut runs as its own
+      conv and comes in as the residual. in_affine applies to x only.
+    upsample2x: the conv reads nearest-2x(x) — x is (B,H/2,W/2,C). GPU: a
+      shift in the A-load address, bit-identical to upsample_nearest2x_nhwc
+      followed by the conv. Opt-in (AIRTC_CONV_UP=1, C % 32 == 0): faster
+      per kernel, within noise on the headline frame; otherwise the separate
+      upsample kernel runs in front of the conv.
 
     GPU path: implicit-GEMM on MFMA with on-the-fly im2col gather and inline
     zero-padding (ops/csrc/conv2d.hip). Weights are lazily pre-transformed
@@ -128,8 +182,44 @@ def conv2d_nhwc(
     if _use_hip(x):
         ext = _require_ext()
         O, I, R, S = weight.shape
-        # Tiny-IC convs at large spatial (the 3/4-channel conv_in layers at
-        # 512²) measured 129us on the scalar small-IC kernel; zero-padding
+        mfma = I % 32 == 0
+        if upsample2x and not (mfma and _switch("AIRTC_CONV_UP", "0")):
+            x = upsample_nearest2x_nhwc(x)
+            upsample2x = False
+        x2 = None
+        if tail is not None:
+            x2, w2, b2 = tail
+            if (mfma and stride == 1 and w2.shape[1] % 32 == 0
+                    and tuple(w2.shape[2:]) == (1, 1) and _use_hip(x2)
+                    and _switch("AIRTC_CONV_TAIL")):
+                x2 = x2.contiguous()
+                if upsample2x:  # one addressing mode per kernel launch
+                    x = upsample_nearest2x_nhwc(x)
+                    upsample2x = False
+            else:
+                # the pair: the shortcut as its own conv, read back as the
+                # residual
+                residual = conv2d_nhwc(x2, w2, b2, 1, 0, residual=residual)
+                x2 = tail = None
+        # 4-/3-channel conv_in layers: lanes-along-OC kernel (conv2d.hip,
+        # conv2d_tinyic_kernel), at any size — at 512²x3->64 it measured
+        # 49.3 us against 55.1 us for the pad-to-32 route below (zeros +
+        # copy_ + MFMA conv). AIRTC_CONV_TINYIC=0 restores the per-pixel
+        # kernel / the pad route.
+        if (I <= 4 and R * S * I <= 36 and in_affine is None
+                and _switch("AIRTC_CONV_TINYIC")):
+            w_tiny = _cached(weight, "_airtc_wtiny", lambda: _tiny_pack(weight))
+            b32 = None
+            if bias is not None:
+                b32 = _cached(bias, "_airtc_b32", lambda: bias.detach().float().contiguous())
+            return ext.conv2d_tinyic(
+                x, w_tiny, b32,
+                None if channel_bias is None else channel_bias.contiguous(),
+                None if residual is None else residual.contiguous(),
+                R, S, stride, padding, act)
+        # Other small-IC convs at large spatial (and the 3/4-channel conv_in
+        # layers with AIRTC_CONV_TINYIC=0) measured 129us at 512² on the
+        # scalar small-IC kernel; zero-padding
         # the input channels to 32 routes them through the MFMA path
         # (numerics identical: zero channels contribute nothing). The pad
         # copy is a ~1.5 MB -> 16 MB expansion, trivial against HBM3E.
@@ -156,6 +246,10 @@ def conv2d_nhwc(
         b32 = None
         if bias is not None:
             b32 = _cached(bias, "_airtc_b32", lambda: bias.detach().float().contiguous())
+        if x2 is not None:
+            # one (O, R*S*I + C2) weight and one summed f32 bias per conv
+            # weight, rebuilt if another shortcut is passed with it
+            w_perm, b32 = _tail_pack(weight, w_perm, bias, tail[1], tail[2])
         args = (
             x,
             w_perm,
@@ -170,8 +264,10 @@ def conv2d_nhwc(
             None if in_affine is None else in_affine.contiguous(),
             in_act,
         )
+        if x2 is not None or upsample2x:
+            args = args + (x2, upsample2x)
         if stats_groups and act == ACT_NONE:
-            y, part = ext.conv2d_stats(*args, stats_groups)
+            y, part = ext.conv2d_stats(*args[:12], stats_groups, *args[12:])
             if part is not None:
                 # (partials, G, version): the norm ignores them if the
                 # tensor was written in place after the conv
@@ -188,8 +284,14 @@ def conv2d_nhwc(
             xf = F.relu(xf)
         x = xf.to(x.dtype)
     xc = x.permute(0, 3, 1, 2)
+    if upsample2x:
+        xc = F.interpolate(xc, scale_factor=2, mode="nearest")
     y = F.conv2d(xc.float(), weight.float(), None if bias is None else bias.float(),
                  stride=stride, padding=padding)
+    if tail is not None:
+        x2, w2, b2 = tail
+        y = y + F.conv2d(x2.permute(0, 3, 1, 2).float(), w2.float(),
+                         None if b2 is None else b2.float())
     y = y.permute(0, 2, 3, 1)
     if channel_bias is not None:
         y = y + channel_bias.float()[:, None, None, :]

@@ -127,18 +127,101 @@ def bench_linear_residual(iters, reps=9):
                   f"{mf / mp:10.3f}  {'SLOWER' if slower else 'ok'}")
 
 
+def bench_conv_operands(iters, reps=9):
+    """Convs that read their operands in place against the kernels they
+    replace: the 1x1 shortcut + conv2 pair against conv2 with a pointwise
+    tail, upsample + conv against nearest-2x in the A-load, and the
+    4-/3-channel conv_in layers on the per-pixel kernel (or the pad-to-32
+    route) against the lanes-along-OC kernel. Same method as the linear
+    rows: device events around `iters` back-to-back calls, `reps` windows
+    per side, sides alternating; eager and replayed from a hipGraph."""
+    dev = "cuda"
+
+    def t(*shape, scale=1.0):
+        return (torch.randn(*shape, device=dev) * scale).half()
+
+    def with_env(name, val, fn):
+        def run():
+            os.environ[name] = val
+            try:
+                return fn()
+            finally:
+                os.environ.pop(name, None)
+        return run
+
+    cases = []
+    # (1) resnet shortcut: hw, cin (the concatenated input), cout
+    for hw, cin, cout in ((64, 960, 320), (32, 1920, 640), (16, 2560, 1280),
+                          (8, 2560, 1280)):
+        x, x2 = t(1, hw, hw, cout), t(1, hw, hw, cin)
+        w, w2 = t(cout, cout, 3, 3, scale=0.02), t(cout, cin, 1, 1, scale=0.02)
+        b, b2 = t(cout), t(cout)
+        cb = t(1, cout)
+        call = (lambda x=x, x2=x2, w=w, w2=w2, b=b, b2=b2, cb=cb:
+                ops.conv2d_nhwc(x, w, b, channel_bias=cb, tail=(x2, w2, b2)))
+        cases.append((f"shortcut {hw}x{hw} {cin}->{cout}",
+                      with_env("AIRTC_CONV_TAIL", "0", call), call))
+    # (2) upsample in front of a conv: source hw, channels
+    for hw, c in ((256, 64), (32, 640)):
+        x, w, b = t(1, hw, hw, c), t(c, c, 3, 3, scale=0.02), t(c)
+        call = lambda x=x, w=w, b=b: ops.conv2d_nhwc(x, w, b, upsample2x=True)
+        cases.append((f"upsample {hw}->{2 * hw} c{c}",
+                      with_env("AIRTC_CONV_UP", "0", call),
+                      with_env("AIRTC_CONV_UP", "1", call)))
+    # (3) tiny-IC conv_in layers
+    for hw, ic, oc in ((64, 4, 320), (64, 4, 64), (512, 3, 64)):
+        x, w, b = t(1, hw, hw, ic), t(oc, ic, 3, 3, scale=0.1), t(oc)
+        old = with_env("AIRTC_CONV_TINYIC", "0",
+                       lambda x=x, w=w, b=b: ops.conv2d_nhwc(x, w, b))
+        wt, b32 = ops.interface._tiny_pack(w), b.float()
+        ext = ops.hip_ext()
+        new = (lambda x=x, wt=wt, b32=b32:
+               ext.conv2d_tinyic(x, wt, b32, None, None, 3, 3, 1, 1, 0))
+        cases.append((f"conv_in {hw}x{hw} {ic}->{oc}", old, new))
+
+    print("== conv operands in place (old = the kernels replaced, new = one "
+          "conv call) ==")
+    print(f"  {'case':>28s} {'mode':>6s}  {'old us (min..max)':>24s}  "
+          f"{'new us (min..max)':>24s}  new/old  verdict")
+    for name, old, new in cases:
+        for fn in (old, new):
+            for _ in range(10):
+                fn()
+        torch.cuda.synchronize()
+        sides = {"eager": (old, new, iters),
+                 "graph": (captured(old, iters), captured(new, iters), 1)}
+        for mode, (fo, fn_, calls) in sides.items():
+            t_o, t_n = [], []
+            for _ in range(reps):
+                t_o.append(window_us(fo, calls) * calls / iters)
+                t_n.append(window_us(fn_, calls) * calls / iters)
+            mo, mn = statistics.median(t_o), statistics.median(t_n)
+            spread = max(max(t_o) - min(t_o), max(t_n) - min(t_n))
+            verdict = ("faster" if mo - mn > spread
+                       else "SLOWER" if mn - mo > spread else "same")
+            print(f"  {name:>28s} {mode:>6s}  "
+                  f"{f'{mo:7.2f} ({min(t_o):.2f}..{max(t_o):.2f})':>24s}  "
+                  f"{f'{mn:7.2f} ({min(t_n):.2f}..{max(t_n):.2f})':>24s}  "
+                  f"{mn / mo:7.3f}  {verdict}")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--iters", type=int, default=50)
     p.add_argument("--batch", type=int, default=1,
                    help="scale conv batch (the fbs>1 serving tier)")
-    p.add_argument("--only", choices=["linear"],
-                   help="run one group: linear = linear + residual")
+    p.add_argument("--only", choices=["linear", "operands"],
+                   help="run one group: linear = linear + residual, "
+                        "operands = convs reading shortcut / upsample / "
+                        "tiny-IC inputs in place")
     args = p.parse_args()
     assert torch.cuda.is_available(), "GPU microbench"
     dev = "cuda"
     if args.only == "linear":
         bench_linear_residual(max(args.iters, 200))
+        return
+    if args.only == "operands":
+        bench_conv_operands(max(args.iters, 100))
         return
 
     print(f"== conv2d (NHWC implicit-GEMM MFMA) B={args.batch} ==")
@@ -254,6 +337,7 @@ def main():
     print(f"  {'preprocess 512x512':32s} {us:8.1f} us  {u8.numel()*3/us/1e3:7.1f} GB/s")
 
     bench_linear_residual(max(args.iters, 200))
+    bench_conv_operands(max(args.iters, 100))
 
 
 if __name__ == "__main__":
