@@ -343,6 +343,11 @@ async def on_startup(app: web.Application) -> None:
         )
         if app.get("fit_mode"):
             cfg.fit_mode = app["fit_mode"]
+        if app.get("output_size"):
+            cfg.output_size = app["output_size"]
+        if app.get("output_max_side") is not None:
+            cfg.output_max_side = app["output_max_side"]
+        cfg.__post_init__()  # validate what was set after construction
         st["pool"] = PipelinePool.create(
             model_id=app["model_id"], n_gpus=app["n_gpus"], cfg=cfg,
             streams_per_replica=app.get("streams_per_gpu", 1),
@@ -382,6 +387,8 @@ def create_app(
     resolution: int = 512,
     streams_per_gpu: int = 1,
     fit_mode: Optional[str] = None,
+    output_size: Optional[str] = None,
+    output_max_side: Optional[int] = None,
 ) -> web.Application:
     app = web.Application(middlewares=[cors_middleware])
     app["model_id"] = model_id
@@ -393,6 +400,9 @@ def create_app(
     app["resolution"] = resolution
     app["streams_per_gpu"] = streams_per_gpu
     app["fit_mode"] = fit_mode  # None: EngineConfig default (AIRTC_FIT_MODE)
+    # None: EngineConfig defaults (AIRTC_OUTPUT_SIZE, AIRTC_OUTPUT_MAX_SIDE)
+    app["output_size"] = output_size
+    app["output_max_side"] = output_max_side
     app["state"] = {
         "pcs": set(),
         "source_track": None,
@@ -436,6 +446,20 @@ def main() -> None:
                              "contain = whole frame with black bars, "
                              "stretch = whole frame, aspect not kept "
                              "(default: $AIRTC_FIT_MODE or cover)")
+    parser.add_argument("--output-size", default=None,
+                        choices=["engine", "source"],
+                        help="size of the frames sent back: engine = "
+                             "--resolution, as ever; source = each session "
+                             "gets the size it publishes (contain loses its "
+                             "bars, cover returns the part of the picture "
+                             "that was used), resized on the GPU "
+                             "(default: $AIRTC_OUTPUT_SIZE or engine)")
+    parser.add_argument("--output-max-side", type=int, default=None,
+                        help="with --output-size source: cap on the longer "
+                             "side of a returned frame, aspect kept; the "
+                             "software encoder's cost grows with the "
+                             "outgoing pixel count (default: "
+                             "$AIRTC_OUTPUT_MAX_SIDE or 0 = no cap)")
     parser.add_argument("--yuv", action="store_true",
                         help="exchange YUV 4:2:0 (I420) frames between the "
                              "codec and the engine instead of packed RGB: "
@@ -482,6 +506,10 @@ def main() -> None:
             # workers are spawned processes: they inherit the environment
             # and EngineConfig.fit_mode defaults from it
             os.environ["AIRTC_FIT_MODE"] = args.fit
+        if args.output_size:
+            os.environ["AIRTC_OUTPUT_SIZE"] = args.output_size
+        if args.output_max_side is not None:
+            os.environ["AIRTC_OUTPUT_MAX_SIDE"] = str(args.output_max_side)
         fe = WorkerFrontend(args.workers, model_id=args.model_id,
                             family=args.family, resolution=args.resolution,
                             pin_gpu=torch.cuda.is_available(),
@@ -495,7 +523,9 @@ def main() -> None:
         return
     app = create_app(model_id=args.model_id, udp_ports=ports, n_gpus=args.gpus,
                      family=args.family, resolution=args.resolution,
-                     streams_per_gpu=args.streams_per_gpu, fit_mode=args.fit)
+                     streams_per_gpu=args.streams_per_gpu, fit_mode=args.fit,
+                     output_size=args.output_size,
+                     output_max_side=args.output_max_side)
     web.run_app(app, host=args.host, port=args.port)
 
 

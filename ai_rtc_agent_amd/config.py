@@ -45,6 +45,12 @@ def _env_float(name: str, default: float) -> float:
 #                                        NVENC_* in reference docs/environment.md:17-25)
 # AIRTC_FIT_MODE (cover|contain|stretch) -> EngineConfig.fit_mode, how frames
 #                                        of another resolution are fitted
+# AIRTC_OUTPUT_SIZE (engine|source)  -> EngineConfig.output_size: return each
+#                                        frame at the engine's size, or at
+#                                        the size its session published
+# AIRTC_OUTPUT_MAX_SIDE (pixels)     -> EngineConfig.output_max_side: cap on
+#                                        the longer side of a returned frame
+#                                        (0 = none)
 # AIRTC_MEDIA_YUV (0|1)              -> media_yuv(): the media plane and the
 #                                        engine exchange I420 frames instead
 #                                        of packed RGB (codec plane I/O, GPU
@@ -93,6 +99,7 @@ def media_yuv() -> bool:
 
 
 OUTPUT_FORMATS = ("rgb", "i420")
+OUTPUT_SIZES = ("engine", "source")
 
 
 @dataclass
@@ -182,6 +189,16 @@ class EngineConfig:
     # frames may be either format whatever this says.
     output_format: str = field(default_factory=lambda: "i420" if media_yuv() else "rgb")
 
+    # any-resolution egress: "engine" = every frame comes back at (height,
+    # width), as ever; "source" = each slot's frame is resized back on the
+    # device to the size its session published (ops.unfit_geometry: contain
+    # loses its bars, cover returns the part of the source that was used),
+    # so a call returns one tensor per slot and their sizes may differ.
+    # output_max_side > 0 caps the longer side of a returned frame: the
+    # software encoder's cost grows with the outgoing pixel count.
+    output_size: str = field(default_factory=lambda: os.environ.get("AIRTC_OUTPUT_SIZE") or "engine")
+    output_max_side: int = field(default_factory=lambda: _env_int("AIRTC_OUTPUT_MAX_SIDE", 0))
+
     # keep the RCFG step (and for cfg full/initialize its extra UNet rows) in
     # the captured graph whatever the initial guidance_scale, so that
     # update_guidance() can raise guidance later, per serving slot, without
@@ -193,6 +210,12 @@ class EngineConfig:
         if self.output_format not in OUTPUT_FORMATS:
             raise ValueError(
                 f"output_format must be one of {OUTPUT_FORMATS}, got {self.output_format!r}")
+        if self.output_size not in OUTPUT_SIZES:
+            raise ValueError(
+                f"output_size must be one of {OUTPUT_SIZES}, got {self.output_size!r}")
+        if not isinstance(self.output_max_side, int) or self.output_max_side < 0:
+            raise ValueError(
+                f"output_max_side must be an int >= 0, got {self.output_max_side!r}")
 
     @property
     def denoising_steps(self) -> int:

@@ -270,6 +270,13 @@ class StreamDiffusionEngine:
         self._slot_ctl: list = [self._slot_defaults() for _ in range(fbs)]
         self._ts_batch = self._coeff["sub_timesteps_tensor"].to(dev)
         self._prev_out: Optional[torch.Tensor] = None
+        # any-resolution egress (cfg.output_size == "source"): per-slot
+        # [Ht, Wt] of the frames last returned (stats) and of the call that
+        # produced _prev_out (the similarity filter never answers a session
+        # with a frame of another size)
+        self._egress = cfg.output_size == "source"
+        self._out_size: list = [None] * fbs
+        self._prev_sizes: Optional[list] = None
         self._graph = None
         self._pipelined = False
         self._last_done = None
@@ -662,6 +669,10 @@ class StreamDiffusionEngine:
         if c["t_index_list"] != d["t_index_list"]:
             self.update_t_index_list(d["t_index_list"], slot)
         self._prev_out = None
+        self._prev_sizes = None
+        if slot < len(self._out_size):
+            self._out_size = list(self._out_size)
+            self._out_size[slot] = None
         if slot < len(self._src_size):
             self._src_size[slot] = None
         if slot < len(self._src_format):
@@ -913,10 +924,12 @@ class StreamDiffusionEngine:
         decoded = self.vae.decode(latent)
         if self.safety_checker is not None:
             decoded = self.safety_checker.filter(decoded)
-        if self.cfg.output_format == "i420":
+        if self.cfg.output_format == "i420" and not self._egress:
             # same launch count: the u8 rounding and the colour conversion
             # are one kernel
             return ops.postprocess_to_i420(decoded)
+        # source-size egress resizes packed RGB: there the colour conversion
+        # belongs to the egress step and the graph is the RGB one
         return ops.postprocess_to_u8(decoded)
 
     @torch.no_grad()
@@ -1080,6 +1093,36 @@ class StreamDiffusionEngine:
         n = 1 if frame_u8.dim() == 3 else frame_u8.shape[0]
         return frame_u8, ["rgb"] * n
 
+    def _egress_targets(self) -> list:
+        """Per slot ((ry, rx, rh, rw), (Ht, Wt)): the window of the engine
+        frame that goes back to the slot's session and the size it goes back
+        at, from the source sizes of this call."""
+        cfg = self.cfg
+        return [
+            ops.unfit_geometry(sz[0], sz[1], cfg.height, cfg.width,
+                               cfg.fit_mode, even=cfg.output_format == "i420",
+                               max_side=cfg.output_max_side)
+            for sz in self._src_size
+        ]
+
+    def _egress_frames(self, frames: torch.Tensor, targets: list) -> list:
+        """The egress step: one fresh tensor per slot out of the finished
+        (fbs, H, W, 3) u8 frames, on the current stream. A slot that reads
+        the whole frame at engine size gets exactly what output_size ==
+        "engine" returns (a copy, or its colour conversion); every other
+        slot is ONE launch of ops.unfit_frame_u8, which for I420 resizes
+        and converts together."""
+        H, W = int(frames.shape[1]), int(frames.shape[2])
+        fmt = self.cfg.output_format
+        outs = []
+        for b, (window, size) in enumerate(targets):
+            if tuple(window) == (0, 0, H, W) and tuple(size) == (H, W):
+                outs.append(ops.rgb_u8_to_i420(frames[b]) if fmt == "i420"
+                            else frames[b].clone())
+            else:
+                outs.append(ops.unfit_frame_u8(frames[b], window, size, fmt))
+        return outs
+
     @torch.no_grad()
     def __call__(self, frame_u8) -> torch.Tensor:
         """frame_u8: (H,W,3) or (fbs,H,W,3) uint8 RGB on any device, or a
@@ -1089,7 +1132,10 @@ class StreamDiffusionEngine:
         instead be an I420 frame ((3Hs/2,Ws), a (fbs,3Hs/2,Ws) batch, or
         list entries of either format): it is converted on the device.
         Returns stylised (H,W,3) / (fbs,H,W,3) uint8 RGB on self.device, or
-        (3H/2,W) / (fbs,3H/2,W) I420 with cfg.output_format == "i420"."""
+        (3H/2,W) / (fbs,3H/2,W) I420 with cfg.output_format == "i420".
+        With cfg.output_size == "source" every slot comes back at the size
+        its source had (ops.unfit_geometry): one tensor for a single-frame
+        call, else a list of fbs tensors whose sizes may differ."""
         assert self._prepared, "call prepare() first"
         cfg = self.cfg
         eng_shape = (cfg.height, cfg.width, 3)
@@ -1140,11 +1186,15 @@ class StreamDiffusionEngine:
                     srcs = None
 
         self._src_format = src_format
+        targets = self._egress_targets() if self._egress else None
+        sizes = [list(t[1]) for t in targets] if self._egress else None
         if self.sim_filter is not None and self._prev_out is not None:
             # on-device pooled cosine (centering + 64x64 avg-pool inside
             # the filter); the only CPU sync is one scalar read that waits
-            # on the frame upload, NOT on the pipelined streams
-            if self.sim_filter.should_skip(frame_u8):
+            # on the frame upload, NOT on the pipelined streams. The filter
+            # sees every frame, but a skip stands only while every slot
+            # still wants the size _prev_out was made at
+            if self.sim_filter.should_skip(frame_u8) and sizes == self._prev_sizes:
                 out = self._prev_out
                 self.timers.frame_done()
                 return out[0] if squeeze else out
@@ -1167,22 +1217,39 @@ class StreamDiffusionEngine:
                     with torch.cuda.stream(self._sB):
                         self._sB.wait_event(self._ev_lat[pp])
                         self._g2[pp].replay()
+                        out = self._out_u8[pp]
+                        if self._egress:
+                            # stream B owns the frame it just decoded: the
+                            # egress reads it here, before done[pp], so
+                            # sync_output() covers the resized frames too
+                            out = self._egress_frames(out, targets)
                         self._ev_done[pp].record()
                     self._last_done = self._ev_done[pp]
-                    out = self._out_u8[pp]
+                    if self._egress:
+                        # allocated on stream B, read on the caller's (the
+                        # mirror of _load_frame_in's sources)
+                        for t in out:
+                            t.record_stream(cur)
                 else:
                     self._load_frame_in(frame_u8, srcs)
                     self._graph.replay()
                     out = self._graph_out
+                    if self._egress:
+                        out = self._egress_frames(out, targets)
             else:
                 self._load_frame_in(frame_u8, srcs)
                 out = self._step_core()
+                if self._egress:
+                    out = self._egress_frames(out, targets)
                 if self._fp8_calib_left:
                     self._fp8_calib_left -= 1
                     if self._fp8_calib_left == 0:
                         self._fp8_freeze()
 
         self._prev_out = out
+        if self._egress:
+            self._prev_sizes = sizes
+            self._out_size = sizes
         self.timers.frame_done()
         return out[0] if squeeze else out
 
@@ -1221,6 +1288,16 @@ class StreamDiffusionEngine:
             # an I420 frame seen), so RGB-only deployments keep the ingest
             # record they had
             d["ingest"]["source_format"] = list(fmts)
+        if self.cfg.output_size == "source":
+            d["egress"] = {
+                "output_size": self.cfg.output_size,
+                "max_side": self.cfg.output_max_side,
+                # last returned [height, width] per slot (None: no frame yet)
+                "last_output_size": [
+                    None if sz is None else list(sz)
+                    for sz in getattr(self, "_out_size", [])
+                ],
+            }
         if self.cfg.use_fp8:
             d["fp8"] = {
                 "active": self.fp8_active,

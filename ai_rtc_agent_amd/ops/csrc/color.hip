@@ -21,19 +21,12 @@
 #include <algorithm>
 
 #include "common.h"
+#include "yuv_math.h"
 
 #define YUV_BLOCK 64  // 512x512 is 16384 lanes: one wave per CU
 #define YUV_MAX_BLOCKS 4096
 
 namespace {
-
-__device__ __forceinline__ uint8_t clip8(int v) {
-  return (uint8_t)min(255, max(0, v));
-}
-
-__device__ __forceinline__ uint8_t luma_of(int r, int g, int b) {
-  return clip8(((66 * r + 129 * g + 25 * b + 128) >> 8) + 16);
-}
 
 // one 2x2 quad: p = {r,g,b} of (row0,x) (row0,x+1) (row1,x) (row1,x+1)
 __device__ __forceinline__ void quad_to_yuv(const uint8_t p[12], uint8_t y[4],
@@ -44,8 +37,7 @@ __device__ __forceinline__ void quad_to_yuv(const uint8_t p[12], uint8_t y[4],
   const int R = (p[0] + p[3] + p[6] + p[9] + 2) >> 2;
   const int G = (p[1] + p[4] + p[7] + p[10] + 2) >> 2;
   const int B = (p[2] + p[5] + p[8] + p[11] + 2) >> 2;
-  cb = clip8(((-38 * R - 74 * G + 112 * B + 128) >> 8) + 128);
-  cr = clip8(((112 * R - 94 * G - 18 * B + 128) >> 8) + 128);
+  chroma_of(R, G, B, cb, cr);
 }
 
 // clip8(v >> 8). The empty asm keeps the shift and the clamp apart: fused,

@@ -7,6 +7,7 @@
 // (guide G11).
 
 #include "common.h"
+#include "yuv_math.h"
 
 #define EW_BLOCK 256
 #define EW_MAX_BLOCKS 2048
@@ -399,6 +400,15 @@ extern "C" void airtc_rcfg_apply(int mode, const uint16_t* eps,
 // the scale at run time, so LDS is fixed (24 KB) and NO downscale factor
 // truncates taps. Source access is byte-wise: no pitch/alignment
 // assumptions (Ws*3 need not be a multiple of 4).
+//
+// I420 = true is the egress form (fit_resize_u8_i420): the destination window
+// is the whole (H, W) picture, H and W even, and dst is its I420 frame
+// (H*W bytes of Y, then (H/2)*(W/2) of Cb, then of Cr, all tight). The tile is
+// computed exactly as above; its rounded u8 values are staged in LDS (the
+// `rows` array is free once the chunk loop is over) and leave the workgroup
+// as planes: one lane per Y pixel, then one lane per chroma sample, both
+// lane-consecutive along a row. FIT_TH and FIT_TW are even, so a 2x2 chroma
+// block never straddles workgroups and no RGB picture is ever written.
 // ---------------------------------------------------------------------------
 #define FIT_TW 64
 #define FIT_TH 8
@@ -417,6 +427,7 @@ __device__ __forceinline__ float fit_weight(float d, float inv_sup) {
   return fmaxf(0.0f, 1.0f - fabsf(d * inv_sup));
 }
 
+template <bool I420>
 __global__ __launch_bounds__(FIT_COLS) void fit_resize_u8_kernel(
     const uint8_t* __restrict__ src, long spitch, uint8_t* __restrict__ dst,
     int H, int W, int y0, int x0, int ch, int cw, int oy, int ox, int oh,
@@ -512,6 +523,51 @@ __global__ __launch_bounds__(FIT_COLS) void fit_resize_u8_kernel(
     __syncthreads();
   }
 
+  if (I420) {
+    // the last __syncthreads() of the chunk loop released `rows`
+    uint8_t* tile = reinterpret_cast<uint8_t*>(rows);
+#pragma unroll
+    for (int t = 0; t < FIT_TH; ++t) {
+      // rows past H and columns past W have no taps: they stage 0 and are
+      // never read back
+      float v = in_x ? nearbyintf(acc[t] * inv_ny[t]) : 0.0f;
+      v = fminf(255.0f, fmaxf(0.0f, v));
+      tile[t * FIT_COLS + tid] = (uint8_t)v;
+    }
+    __syncthreads();
+    const int tx0 = blockIdx.x * FIT_TW;
+    const long plane = (long)H * W;
+    // Y: one lane per pixel, FIT_TW consecutive lanes per tile row
+    for (int i = tid; i < FIT_TH * FIT_TW; i += FIT_COLS) {
+      const int ly = i / FIT_TW, lx = i - ly * FIT_TW;
+      const int y = ty0 + ly, x = tx0 + lx;
+      if (y < H && x < W) {
+        const uint8_t* p = tile + ly * FIT_COLS + lx * 3;
+        dst[(long)y * W + x] = luma_of(p[0], p[1], p[2]);
+      }
+    }
+    // Cb, Cr: one lane per 2x2 block. H and W are even, so a block whose
+    // top-left pixel is inside the picture is wholly inside it
+    if (tid < (FIT_TH / 2) * (FIT_TW / 2)) {
+      const int ly = tid / (FIT_TW / 2), lx = tid - ly * (FIT_TW / 2);
+      const int y = ty0 + 2 * ly, x = tx0 + 2 * lx;
+      if (y < H && x < W) {
+        const uint8_t* p0 = tile + (2 * ly) * FIT_COLS + lx * 6;
+        const uint8_t* p1 = p0 + FIT_COLS;
+        const int R = (p0[0] + p0[3] + p1[0] + p1[3] + 2) >> 2;
+        const int G = (p0[1] + p0[4] + p1[1] + p1[4] + 2) >> 2;
+        const int B = (p0[2] + p0[5] + p1[2] + p1[5] + 2) >> 2;
+        uint8_t cb, cr;
+        chroma_of(R, G, B, cb, cr);
+        // chroma planes are flat bytes: row pitch W/2 whatever H/2 is
+        const long c = plane + (long)(y >> 1) * (W >> 1) + (x >> 1);
+        dst[c] = cb;
+        dst[c + plane / 4] = cr;
+      }
+    }
+    return;
+  }
+
   if (!col_ok) return;
 #pragma unroll
   for (int t = 0; t < FIT_TH; ++t) {
@@ -528,6 +584,17 @@ extern "C" void airtc_fit_resize_u8(const uint8_t* src, int Ws, uint8_t* dst,
                                     int cw, int oy, int ox, int oh, int ow,
                                     hipStream_t s) {
   dim3 grid((W * 3 + FIT_COLS - 1) / FIT_COLS, (H + FIT_TH - 1) / FIT_TH);
-  hipLaunchKernelGGL(fit_resize_u8_kernel, grid, dim3(FIT_COLS), 0, s, src,
-                     (long)Ws * 3, dst, H, W, y0, x0, ch, cw, oy, ox, oh, ow);
+  hipLaunchKernelGGL(fit_resize_u8_kernel<false>, grid, dim3(FIT_COLS), 0, s,
+                     src, (long)Ws * 3, dst, H, W, y0, x0, ch, cw, oy, ox, oh,
+                     ow);
+}
+
+// window (y0, x0, ch, cw) of src -> the whole (H, W) picture as I420 in dst
+extern "C" void airtc_fit_resize_u8_i420(const uint8_t* src, int Ws,
+                                         uint8_t* dst, int H, int W, int y0,
+                                         int x0, int ch, int cw,
+                                         hipStream_t s) {
+  dim3 grid((W + FIT_TW - 1) / FIT_TW, (H + FIT_TH - 1) / FIT_TH);
+  hipLaunchKernelGGL(fit_resize_u8_kernel<true>, grid, dim3(FIT_COLS), 0, s,
+                     src, (long)Ws * 3, dst, H, W, y0, x0, ch, cw, 0, 0, H, W);
 }

@@ -405,6 +405,33 @@ void fit_resize_u8(torch::Tensor src, torch::Tensor dst, int64_t slot,
                       (int)ox, (int)oh, (int)ow, cur_stream());
 }
 
+// egress: window (y0,x0,ch,cw) of src (Hs,Ws,3) -> dst, a whole I420 frame
+// (3H/2, W); the target size is dst's
+void fit_resize_u8_i420(torch::Tensor src, torch::Tensor dst, int64_t y0,
+                        int64_t x0, int64_t ch, int64_t cw) {
+  CHECK_IN(src);
+  CHECK_IN(dst);
+  TORCH_CHECK(src.dtype() == torch::kUInt8 && dst.dtype() == torch::kUInt8);
+  TORCH_CHECK(src.device() == dst.device(), "src/dst on different devices");
+  TORCH_CHECK(src.dim() == 3 && src.size(2) == 3, "src must be (Hs, Ws, 3)");
+  TORCH_CHECK(dst.dim() == 2, "dst must be (3H/2, W)");
+  const int64_t Hs = src.size(0), Ws = src.size(1);
+  const int64_t R = dst.size(0), W = dst.size(1);
+  TORCH_CHECK(R >= 3 && R % 3 == 0 && W >= 2 && W % 2 == 0,
+              "I420 needs (3H/2, W) with even H, W >= 2, got ", R, "x", W);
+  const int64_t H = R / 3 * 2;
+  TORCH_CHECK(Hs >= 1 && Ws >= 1, "empty frame");
+  TORCH_CHECK(Hs * Ws * 3 < (1LL << 31) && H * W * 3 < (1LL << 31),
+              "frame too large");
+  // the kernel trusts this window for every load
+  TORCH_CHECK(ch >= 1 && cw >= 1 && y0 >= 0 && x0 >= 0 && y0 + ch <= Hs &&
+                  x0 + cw <= Ws,
+              "source window out of range");
+  airtc_fit_resize_u8_i420(src.data_ptr<uint8_t>(), (int)Ws,
+                           dst.data_ptr<uint8_t>(), (int)H, (int)W, (int)y0,
+                           (int)x0, (int)ch, (int)cw, cur_stream());
+}
+
 // --- I420 colour conversion (color.hip) --------------------------------
 // shared validation: packed side `rgb` (B,H,W,3) of dtype rgb_dt, planar
 // side (B,3H/2,W) u8; `out` is the caller's tensor or a fresh one
@@ -939,6 +966,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("postprocess_u8", &postprocess_u8);
   m.def("fit_resize_u8", &fit_resize_u8,
         "crop + antialiased resize of a u8 RGB frame into one slot");
+  m.def("fit_resize_u8_i420", &fit_resize_u8_i420,
+        "crop + antialiased resize of a u8 RGB frame into a whole I420 frame");
   m.def("rgb_u8_to_i420", &rgb_u8_to_i420,
         "(B,H,W,3) u8 RGB -> (B,3H/2,W) u8 I420 (BT.601 limited, integer)",
         pybind11::arg("x"), pybind11::arg("out") = pybind11::none());

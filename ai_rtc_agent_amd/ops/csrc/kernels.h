@@ -25,6 +25,11 @@ void airtc_upsample2x_f16(const uint16_t* in, uint16_t* out, int B, int H,
 void airtc_fit_resize_u8(const uint8_t* src, int Ws, uint8_t* dst, int H,
                          int W, int y0, int x0, int ch, int cw, int oy,
                          int ox, int oh, int ow, hipStream_t s);
+// same resize of window (y0,x0,ch,cw) into a whole (H,W) picture, H and W
+// even, written as its I420 frame (3H/2, W) in the same launch
+void airtc_fit_resize_u8_i420(const uint8_t* src, int Ws, uint8_t* dst, int H,
+                              int W, int y0, int x0, int ch, int cw,
+                              hipStream_t s);
 // colour (color.hip) --------------------------------------------------------
 // I420 frame = (3H/2, W) u8: H*W of Y, then (H/2)*(W/2) of Cb, then of Cr,
 // tight; BT.601 limited range in the software codec's integer arithmetic.

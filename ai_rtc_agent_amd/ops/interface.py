@@ -1114,6 +1114,98 @@ def postprocess_to_i420(img: torch.Tensor, out: torch.Tensor | None = None) -> t
     return _finish(res, out, squeeze)
 
 
+def unfit_geometry(Hs: int, Ws: int, H: int, W: int, mode: str = "cover",
+                   even: bool = False, max_side: int = 0):
+    """Inverse of fit_geometry: how a (H, W) engine frame goes back to a
+    session that published (Hs, Ws).
+
+    Returns ((ry, rx, rh, rw), (Ht, Wt)): the window of the engine frame to
+    read and the size of the frame to hand back.
+      stretch — whole frame, back to (Hs, Ws)
+      contain — the ingest's destination window (the bars are cut away),
+                back to (Hs, Ws)
+      cover   — whole frame, back to the source window the ingest used
+                (ch, cw); the cropped edges are not invented
+    Then, in this order: max_side > 0 scales both sides so that the longer
+    one is exactly max_side (only ever down), and `even` floors both sides
+    to even, at least 2 (I420)."""
+    (_, _, ch, cw), (oy, ox, oh, ow) = fit_geometry(Hs, Ws, H, W, mode)
+    if max_side < 0:
+        raise ValueError(f"max_side must be >= 0, got {max_side}")
+    if mode == "contain":
+        window, (Ht, Wt) = (oy, ox, oh, ow), (Hs, Ws)
+    elif mode == "cover":
+        window, (Ht, Wt) = (0, 0, H, W), (ch, cw)
+    else:
+        window, (Ht, Wt) = (0, 0, H, W), (Hs, Ws)
+    longer = max(Ht, Wt)
+    if max_side > 0 and longer > max_side:
+        Ht, Wt = _round_div(Ht, max_side, longer), _round_div(Wt, max_side, longer)
+    if even:
+        Ht, Wt = max(2, Ht - Ht % 2), max(2, Wt - Wt % 2)
+    return window, (Ht, Wt)
+
+
+def unfit_frame_u8(img: torch.Tensor, window, size, fmt: str = "rgb",
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+    """Resize a window of one engine frame to a session's own size.
+
+    img: (H, W, 3) u8 contiguous; window = (ry, rx, rh, rw) inside it;
+    size = (Ht, Wt). fmt="rgb" returns (Ht, Wt, 3) u8, fmt="i420" returns
+    the (3*Ht/2, Wt) I420 frame (Ht, Wt even) that is, bit for bit,
+    rgb_u8_to_i420 of the RGB result. The filter is fit_frame_u8's:
+    separable antialiased triangle, f32 accumulation, round-half-even,
+    clamp, taps clamped to the window; an equal-size window is an exact
+    copy. `out`, when given, is written in place.
+
+    GPU: ONE launch on the current stream either way: fit_resize_u8 for RGB,
+    fit_resize_u8_i420 (the same resize with the colour conversion done on
+    the tile before it leaves the workgroup) for I420. CPU tensors and
+    AIRTC_FORCE_EAGER=1 take the torch reference."""
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8:
+        raise TypeError("unfit_frame_u8 takes a uint8 tensor")
+    if img.dim() != 3 or img.shape[-1] != 3:
+        raise ValueError(f"unfit_frame_u8 needs img (H,W,3), got {tuple(img.shape)}")
+    if fmt not in ("rgb", "i420"):
+        raise ValueError(f"fmt must be 'rgb' or 'i420', got {fmt!r}")
+    H, W = int(img.shape[0]), int(img.shape[1])
+    ry, rx, rh, rw = (int(v) for v in window)
+    Ht, Wt = (int(v) for v in size)
+    if min(rh, rw) < 1 or min(ry, rx) < 0 or ry + rh > H or rx + rw > W:
+        raise ValueError(f"window {(ry, rx, rh, rw)} is not inside {(H, W)}")
+    if min(Ht, Wt) < 1:
+        raise ValueError(f"empty target size {(Ht, Wt)}")
+    if fmt == "i420" and (Ht < 2 or Wt < 2 or Ht % 2 or Wt % 2):
+        raise ValueError(f"I420 needs even H, W >= 2, got {Ht}x{Wt}")
+    shape = (Ht, Wt, 3) if fmt == "rgb" else (Ht // 2 * 3, Wt)
+    _check_out(out, img, shape)
+    if _on_kernel(img):
+        if not img.is_contiguous():
+            raise ValueError("img must be contiguous")
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=img.device)
+        if fmt == "rgb":
+            _require_ext().fit_resize_u8(img, out.unsqueeze(0), 0, ry, rx, rh,
+                                         rw, 0, 0, Ht, Wt)
+        else:
+            _require_ext().fit_resize_u8_i420(img, out, ry, rx, rh, rw)
+        return out
+    win = img[ry:ry + rh, rx:rx + rw]
+    if (rh, rw) != (Ht, Wt):
+        x = win.permute(2, 0, 1).unsqueeze(0).to(torch.float32)
+        x = F.interpolate(x, size=(Ht, Wt), mode="bilinear", antialias=True,
+                          align_corners=False)
+        win = x.round().clamp(0, 255).to(torch.uint8)[0].permute(1, 2, 0)
+    # contiguous, and never a view of img
+    res = win.clone(memory_format=torch.contiguous_format)
+    if fmt == "i420":
+        res = _rgb_u8_to_i420_ref(res.unsqueeze(0))[0]
+    if out is None:
+        return res
+    out.copy_(res)
+    return out
+
+
 def i420_to_rgb_u8(x: torch.Tensor, H: int | None = None,
                    out: torch.Tensor | None = None) -> torch.Tensor:
     """I420 (3H/2,W) / (B,3H/2,W) -> u8 RGB (H,W,3) / (B,H,W,3).
