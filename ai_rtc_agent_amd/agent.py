@@ -220,6 +220,14 @@ def _checked_config(params) -> dict:
             if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
                 raise ValueError(f"{key} must be a finite number")
             out[key] = float(v)
+    for key in ("canny_low", "canny_high"):
+        v = params.get(key)
+        if v is not None:
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 2040:
+                raise ValueError(f"{key} must be an integer in [0, 2040]")
+            out[key] = v
+    if "canny_low" in out and "canny_high" in out and out["canny_low"] > out["canny_high"]:
+        raise ValueError("canny_low must not exceed canny_high")
     return out
 
 
@@ -246,6 +254,8 @@ def _apply_checked(pipeline, cfg: dict) -> None:
         pipeline.update_negative_prompt(cfg["negative_prompt"])
     if "guidance_scale" in cfg or "delta" in cfg:
         pipeline.update_guidance(cfg.get("guidance_scale"), cfg.get("delta"))
+    if "canny_low" in cfg or "canny_high" in cfg:
+        pipeline.update_canny(cfg.get("canny_low"), cfg.get("canny_high"))
 
 
 def _apply_session_config(pipeline, msg) -> None:
@@ -347,6 +357,13 @@ async def on_startup(app: web.Application) -> None:
             cfg.output_size = app["output_size"]
         if app.get("output_max_side") is not None:
             cfg.output_max_side = app["output_max_side"]
+        for key in ("controlnet_processor", "controlnet_scale", "canny_low",
+                    "canny_high", "canny_reach"):
+            if app.get(key) is not None:
+                setattr(cfg, key, app[key])
+        if cfg.controlnet_processor != "none":
+            # a conditioning processor is only ever wanted with its ControlNet
+            cfg.use_controlnet = True
         cfg.__post_init__()  # validate what was set after construction
         st["pool"] = PipelinePool.create(
             model_id=app["model_id"], n_gpus=app["n_gpus"], cfg=cfg,
@@ -389,6 +406,11 @@ def create_app(
     fit_mode: Optional[str] = None,
     output_size: Optional[str] = None,
     output_max_side: Optional[int] = None,
+    controlnet_processor: Optional[str] = None,
+    controlnet_scale: Optional[float] = None,
+    canny_low: Optional[int] = None,
+    canny_high: Optional[int] = None,
+    canny_reach: Optional[int] = None,
 ) -> web.Application:
     app = web.Application(middlewares=[cors_middleware])
     app["model_id"] = model_id
@@ -403,6 +425,13 @@ def create_app(
     # None: EngineConfig defaults (AIRTC_OUTPUT_SIZE, AIRTC_OUTPUT_MAX_SIDE)
     app["output_size"] = output_size
     app["output_max_side"] = output_max_side
+    # None: EngineConfig defaults (AIRTC_CONTROLNET_PROCESSOR, AIRTC_CANNY_*);
+    # a processor other than "none" switches the ControlNet on
+    app["controlnet_processor"] = controlnet_processor
+    app["controlnet_scale"] = controlnet_scale
+    app["canny_low"] = canny_low
+    app["canny_high"] = canny_high
+    app["canny_reach"] = canny_reach
     app["state"] = {
         "pcs": set(),
         "source_track": None,
@@ -471,6 +500,28 @@ def main() -> None:
                              "whatever the initial guidance_scale, so a "
                              "session can raise its guidance at runtime "
                              "(same as AIRTC_RUNTIME_GUIDANCE=1)")
+    parser.add_argument("--controlnet-processor", default=None,
+                        choices=["none", "canny"],
+                        help="turn each live frame into the ControlNet's "
+                             "hint: canny = edge map computed on the GPU "
+                             "inside the captured graph, every in-flight "
+                             "stage conditioned on its own frame; any value "
+                             "but none switches the ControlNet on (default: "
+                             "$AIRTC_CONTROLNET_PROCESSOR or none)")
+    parser.add_argument("--controlnet-scale", type=float, default=None,
+                        help="weight of the ControlNet residuals (default: "
+                             "$AIRTC_CONTROLNET_SCALE or 1.0)")
+    parser.add_argument("--canny-low", type=int, default=None,
+                        help="lower hysteresis threshold on the L1 gradient "
+                             "magnitude, 0..2040; per session at runtime via "
+                             "POST /config (default: $AIRTC_CANNY_LOW or 100)")
+    parser.add_argument("--canny-high", type=int, default=None,
+                        help="upper hysteresis threshold "
+                             "(default: $AIRTC_CANNY_HIGH or 200)")
+    parser.add_argument("--canny-reach", type=int, default=None,
+                        help="how many 3x3 steps a weak edge may lie from a "
+                             "strong one, 0..32; cv2.Canny's hysteresis is "
+                             "unbounded (default: $AIRTC_CANNY_REACH or 16)")
     parser.add_argument("--streams-per-gpu", type=int, default=1,
                         help="multi-stream batched serving: sessions per "
                              "GPU batched through one engine (fbs=K; "
@@ -510,6 +561,13 @@ def main() -> None:
             os.environ["AIRTC_OUTPUT_SIZE"] = args.output_size
         if args.output_max_side is not None:
             os.environ["AIRTC_OUTPUT_MAX_SIDE"] = str(args.output_max_side)
+        for flag, env in (("controlnet_processor", "AIRTC_CONTROLNET_PROCESSOR"),
+                          ("controlnet_scale", "AIRTC_CONTROLNET_SCALE"),
+                          ("canny_low", "AIRTC_CANNY_LOW"),
+                          ("canny_high", "AIRTC_CANNY_HIGH"),
+                          ("canny_reach", "AIRTC_CANNY_REACH")):
+            if getattr(args, flag) is not None:
+                os.environ[env] = str(getattr(args, flag))
         fe = WorkerFrontend(args.workers, model_id=args.model_id,
                             family=args.family, resolution=args.resolution,
                             pin_gpu=torch.cuda.is_available(),
@@ -525,7 +583,11 @@ def main() -> None:
                      family=args.family, resolution=args.resolution,
                      streams_per_gpu=args.streams_per_gpu, fit_mode=args.fit,
                      output_size=args.output_size,
-                     output_max_side=args.output_max_side)
+                     output_max_side=args.output_max_side,
+                     controlnet_processor=args.controlnet_processor,
+                     controlnet_scale=args.controlnet_scale,
+                     canny_low=args.canny_low, canny_high=args.canny_high,
+                     canny_reach=args.canny_reach)
     web.run_app(app, host=args.host, port=args.port)
 
 

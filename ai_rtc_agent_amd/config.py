@@ -59,6 +59,16 @@ def _env_float(name: str, default: float) -> float:
 # AIRTC_RUNTIME_GUIDANCE (0|1)       -> EngineConfig.runtime_guidance: keep
 #                                        the RCFG step in the captured graph
 #                                        so guidance can be raised at runtime
+# AIRTC_CONTROLNET_PROCESSOR (none|canny) -> EngineConfig.controlnet_processor:
+#                                        what turns the live frame into the
+#                                        ControlNet's hint
+# AIRTC_CONTROLNET_SCALE (float)     -> EngineConfig.controlnet_scale
+# AIRTC_CANNY_LOW / AIRTC_CANNY_HIGH  -> EngineConfig.canny_low / canny_high,
+#                                        hysteresis thresholds on the L1
+#                                        gradient magnitude (0..2040)
+# AIRTC_CANNY_REACH (0..32)           -> EngineConfig.canny_reach: how many
+#                                        3x3 steps a weak edge may lie from a
+#                                        strong one
 
 
 def engines_cache_dir() -> str:
@@ -100,6 +110,7 @@ def media_yuv() -> bool:
 
 OUTPUT_FORMATS = ("rgb", "i420")
 OUTPUT_SIZES = ("engine", "source")
+CONTROLNET_PROCESSORS = ("none", "canny")
 
 
 @dataclass
@@ -153,7 +164,7 @@ class EngineConfig:
     lcm_lora_id: Optional[str] = None
     vae_id: Optional[str] = None
     use_controlnet: bool = False
-    controlnet_scale: float = 1.0
+    controlnet_scale: float = field(default_factory=lambda: _env_float("AIRTC_CONTROLNET_SCALE", 1.0))
     use_safety_checker: bool = False
     similarity_filter: SimilarityFilterConfig = field(default_factory=SimilarityFilterConfig)
     encoder: EncoderConfig = field(default_factory=EncoderConfig)
@@ -206,7 +217,38 @@ class EngineConfig:
     # guidance math in its hot path at all (the benchmarked graphs).
     runtime_guidance: bool = field(default_factory=lambda: _env_bool("AIRTC_RUNTIME_GUIDANCE", False))
 
+    # ControlNet conditioning processor (use_controlnet, img2img): "none"
+    # hands the ControlNet the normalised input frame itself, the newest
+    # frame's for every in-flight stage; "canny" turns each new frame into
+    # the edge map an edge ControlNet was trained on (ops.canny_hint, inside
+    # the captured graph), encodes it once and keeps the encoded hints of the
+    # in-flight stages in a FIFO beside the latent buffer, so every stage is
+    # conditioned on its own frame. canny_low/canny_high are thresholds on
+    # the L1 gradient magnitude (<= 2040), per serving slot at run time
+    # (update_canny); canny_reach bounds the hysteresis to that many 3x3
+    # steps from a strong edge (cv2.Canny's is unbounded) and is fixed for
+    # the life of the engine.
+    controlnet_processor: str = field(default_factory=lambda: os.environ.get("AIRTC_CONTROLNET_PROCESSOR") or "none")
+    canny_low: int = field(default_factory=lambda: _env_int("AIRTC_CANNY_LOW", 100))
+    canny_high: int = field(default_factory=lambda: _env_int("AIRTC_CANNY_HIGH", 200))
+    canny_reach: int = field(default_factory=lambda: _env_int("AIRTC_CANNY_REACH", 16))
+
     def __post_init__(self) -> None:
+        if self.controlnet_processor not in CONTROLNET_PROCESSORS:
+            raise ValueError(
+                f"controlnet_processor must be one of {CONTROLNET_PROCESSORS}, "
+                f"got {self.controlnet_processor!r}")
+        for name in ("canny_low", "canny_high", "canny_reach"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"{name} must be an int, got {v!r}")
+        if not 0 <= self.canny_low <= self.canny_high <= 2040:
+            raise ValueError(
+                f"canny thresholds need 0 <= canny_low <= canny_high <= 2040, "
+                f"got {self.canny_low}, {self.canny_high}")
+        if not 0 <= self.canny_reach <= 32:
+            raise ValueError(
+                f"canny_reach must be in [0, 32], got {self.canny_reach}")
         if self.output_format not in OUTPUT_FORMATS:
             raise ValueError(
                 f"output_format must be one of {OUTPUT_FORMATS}, got {self.output_format!r}")

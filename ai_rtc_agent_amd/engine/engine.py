@@ -254,6 +254,19 @@ class StreamDiffusionEngine:
         g = torch.Generator(device="cpu").manual_seed(cfg.seed)
         self._init_noise = torch.randn((B, lh, lw, 4), generator=g).to(dev, dt)
         self._x_t_buffer = torch.zeros((max(0, B - fbs), lh, lw, 4), device=dev, dtype=dt)
+        # controlnet_processor == "canny": the encoded edge hints of the
+        # in-flight stages, row for row beside _x_t_buffer (stage i+1 of
+        # the next round reads what stage i read in this one), and the
+        # per-slot (low, high) thresholds the kernel reads from memory
+        self._canny = (cfg.controlnet_processor == "canny"
+                       and self.controlnet is not None and cfg.mode == "img2img")
+        self._hint_feat_buffer = None
+        self._canny_thr = None
+        if self._canny:
+            c0 = self.controlnet.cfg.block_out_channels[0]
+            self._hint_feat_buffer = torch.zeros((max(0, B - fbs), lh, lw, c0), device=dev, dtype=dt)
+            self._canny_thr = torch.tensor(
+                [[cfg.canny_low, cfg.canny_high]] * fbs, dtype=torch.int32).to(dev)
         self.rcfg.reset(self._init_noise)
 
         # static I/O buffers (graph-stable addresses); _frame_in (u8) is the
@@ -394,13 +407,17 @@ class StreamDiffusionEngine:
     # ------------------------------------------------------------------
     def _slot_defaults(self) -> dict:
         cfg = self.cfg
-        return {
+        d = {
             "prompt": self.prompt,
             "negative_prompt": cfg.negative_prompt,
             "guidance_scale": float(cfg.guidance_scale),
             "delta": float(cfg.delta),
             "t_index_list": list(cfg.t_index_list),
         }
+        if getattr(self, "_canny", False):
+            d["canny_low"] = int(cfg.canny_low)
+            d["canny_high"] = int(cfg.canny_high)
+        return d
 
     def _set_ctl(self, slot: Optional[int], **kw) -> None:
         for c in (self._slot_ctl if slot is None else [self._slot_ctl[slot]]):
@@ -414,7 +431,8 @@ class StreamDiffusionEngine:
 
     def slot_controls(self, slot: int) -> dict:
         """The slot's current prompt, negative_prompt, guidance_scale, delta
-        and t_index_list (host-side copies; nothing is read from the GPU)."""
+        and t_index_list, and with the canny processor canny_low and
+        canny_high (host-side copies; nothing is read from the GPU)."""
         self._check_slot(slot)
         c = dict(self._slot_ctl[slot])
         c["t_index_list"] = list(c["t_index_list"])
@@ -573,6 +591,44 @@ class StreamDiffusionEngine:
                 cfg.delta = d
         self._set_ctl(slot, **kw)
 
+    @torch.no_grad()
+    def update_canny(self, low: Optional[int] = None, high: Optional[int] = None,
+                     slot: Optional[int] = None) -> None:
+        """Change the Canny thresholds (0 <= low <= high <= 2040, on the L1
+        gradient magnitude) of one serving slot, or of every slot and the
+        replica defaults: an in-place write of the (fbs, 2) tensor the edge
+        kernel reads from memory, never a re-capture. A value left None
+        keeps what the slot has. The frames already in flight keep the hints
+        they were encoded with; the next frame is the first to see the new
+        thresholds."""
+        self._check_slot(slot)
+        if not self._canny:
+            raise ValueError(
+                "canny thresholds need controlnet_processor='canny' on an "
+                "img2img engine with use_controlnet")
+        fbs = self.cfg.frame_buffer_size
+        slots = range(fbs) if slot is None else [slot]
+        pairs = {
+            s: ops.check_canny_thresholds(
+                self._slot_ctl[s]["canny_low"] if low is None else low,
+                self._slot_ctl[s]["canny_high"] if high is None else high)
+            for s in slots
+        }
+        if slot is None:
+            # the replica defaults (what reset_slot restores) move too and
+            # must stay a valid pair themselves
+            default = ops.check_canny_thresholds(
+                self.cfg.canny_low if low is None else low,
+                self.cfg.canny_high if high is None else high)
+        rows = torch.tensor([pairs[s] for s in slots], dtype=torch.int32).to(self.device)
+        with self._row_writes(rows):
+            (self._canny_thr if slot is None
+             else self._canny_thr[slot:slot + 1]).copy_(rows)
+        for s, (lo, hi) in pairs.items():
+            self._slot_ctl[s].update(canny_low=lo, canny_high=hi)
+        if slot is None:
+            self.cfg.canny_low, self.cfg.canny_high = default
+
     def _reprepare(self, guidance_scale: Optional[float] = None,
                    delta: Optional[float] = None,
                    t_index_list: Optional[list] = None) -> None:
@@ -606,6 +662,9 @@ class StreamDiffusionEngine:
                 self.update_guidance(g, d, slot)
             if c["t_index_list"] != old["t_index_list"] and len(c["t_index_list"]) == n:
                 self.update_t_index_list(c["t_index_list"], slot)
+            if self._canny and (c["canny_low"], c["canny_high"]) != (
+                    old["canny_low"], old["canny_high"]):
+                self.update_canny(c["canny_low"], c["canny_high"], slot)
 
     @staticmethod
     def _tensors_of(coeff: dict) -> list:
@@ -655,6 +714,9 @@ class StreamDiffusionEngine:
         with self._row_writes():
             if self._x_t_buffer.shape[0]:
                 slot_rows(self._x_t_buffer, slot, fbs).zero_()
+            if self._canny and self._hint_feat_buffer.shape[0]:
+                # the previous tenant's edges must not condition the new one
+                slot_rows(self._hint_feat_buffer, slot, fbs).zero_()
             stock = self.rcfg.stock_noise
             if stock is not None and stock.shape == self._init_noise.shape:
                 slot_rows(stock, slot, fbs).copy_(slot_rows(self._init_noise, slot, fbs))
@@ -668,6 +730,9 @@ class StreamDiffusionEngine:
             self.update_guidance(d["guidance_scale"], d["delta"], slot)
         if c["t_index_list"] != d["t_index_list"]:
             self.update_t_index_list(d["t_index_list"], slot)
+        if self._canny and (c["canny_low"], c["canny_high"]) != (
+                d["canny_low"], d["canny_high"]):
+            self.update_canny(d["canny_low"], d["canny_high"], slot)
         self._prev_out = None
         self._prev_sizes = None
         if slot < len(self._out_size):
@@ -893,10 +958,35 @@ class StreamDiffusionEngine:
         unet_ts = self._unet_batch_timesteps()
         unet_emb = self._unet_batch_embeds()
         control = None
-        if self.controlnet is not None and cfg.mode == "img2img":
-            # hint = the current input frame (per in-flight stage we reuse
-            # the newest frame's hint; per-stage hints would need a hint
-            # FIFO mirroring the latent buffer)
+        if self._canny:
+            # per-stage hints: the edge map of the fbs NEW frames is encoded
+            # once; the in-flight stages read the features their frames were
+            # encoded to, kept stage-major exactly like x_t
+            hint0 = ops.canny_hint(self._frame_in, self._canny_thr,
+                                   cfg.canny_reach, self.dtype)
+            feat0 = self.controlnet.hint_encoder(hint0)
+            buf = self._hint_feat_buffer
+            feat = torch.cat([feat0, buf], dim=0) if buf.shape[0] else feat0
+            # the extra RCFG rows mirror _unet_batch_input
+            if cfg.cfg_type == "full" and self.rcfg.active:
+                unet_feat = torch.cat([feat, feat], dim=0)
+            elif cfg.cfg_type == "initialize" and self.rcfg.active:
+                unet_feat = torch.cat([feat[:fbs], feat], dim=0)
+            else:
+                unet_feat = feat
+            control = self.controlnet(
+                unet_in, unet_ts, unet_emb, scale=cfg.controlnet_scale,
+                hint_features=unet_feat,
+            )
+            if buf.shape[0]:
+                # stage i's features become stage i+1's, in step with the
+                # latent shift below
+                buf.copy_(feat[:-fbs])
+        elif self.controlnet is not None and cfg.mode == "img2img":
+            # processor "none": hint = the current input frame (per
+            # in-flight stage we reuse the newest frame's hint; the canny
+            # branch above keeps per-stage hints in a FIFO mirroring the
+            # latent buffer)
             hint = self._img_proc.expand(unet_in.shape[0], -1, -1, -1).contiguous()
             control = self.controlnet(
                 unet_in, unet_ts, unet_emb, hint, scale=cfg.controlnet_scale
@@ -1297,6 +1387,15 @@ class StreamDiffusionEngine:
                     None if sz is None else list(sz)
                     for sz in getattr(self, "_out_size", [])
                 ],
+            }
+        if getattr(self, "_canny", False):
+            d["controlnet"] = {
+                "processor": self.cfg.controlnet_processor,
+                "scale": float(self.cfg.controlnet_scale),
+                "canny_reach": self.cfg.canny_reach,
+                # [low, high] per slot, as last written
+                "canny_thresholds": [
+                    [c["canny_low"], c["canny_high"]] for c in self._slot_ctl],
             }
         if self.cfg.use_fp8:
             d["fp8"] = {

@@ -13,7 +13,7 @@ the UNet so the HIP kernels cover it with no new ops.
 """
 from __future__ import annotations
 
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -100,14 +100,24 @@ class ControlNet(nn.Module):
         sample: torch.Tensor,
         timesteps: torch.Tensor,
         encoder_hidden_states: torch.Tensor,
-        hint: torch.Tensor,
+        hint: Optional[torch.Tensor] = None,
         scale: float = 1.0,
+        *,
+        hint_features: Optional[torch.Tensor] = None,
     ) -> Tuple[List[torch.Tensor], torch.Tensor]:
-        """Returns (skip_residuals — one per UNet skip entry, mid_residual)."""
+        """Returns (skip_residuals — one per UNet skip entry, mid_residual).
+        Exactly one of `hint` (B,H,W,3), encoded here, and `hint_features`
+        (B,H/8,W/8,C0), the output of hint_encoder computed by the caller
+        (the engine encodes each frame once and keeps the rows of the
+        in-flight stages), is given."""
+        if (hint is None) == (hint_features is None):
+            raise ValueError("pass exactly one of hint and hint_features")
         cfg = self.cfg
         temb = timestep_embedding(timesteps, self.time_proj_dim).to(sample.dtype)
         temb = self.time_embed[1](ops.silu(self.time_embed[0](temb)))
-        h = self.conv_in(sample) + self.hint_encoder(hint)
+        if hint_features is None:
+            hint_features = self.hint_encoder(hint)
+        h = self.conv_in(sample) + hint_features
         outs = [self.zero_convs[0](h) * scale]
         zi = 1
         ri = 0

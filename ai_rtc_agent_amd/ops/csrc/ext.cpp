@@ -499,6 +499,37 @@ torch::Tensor i420_to_rgb_u8(torch::Tensor x,
   return o;
 }
 
+// --- Canny edge hint (canny.hip) ---------------------------------------
+torch::Tensor canny_hint(torch::Tensor frames, torch::Tensor thr,
+                         int64_t reach, torch::Tensor out) {
+  CHECK_IN(frames);
+  CHECK_IN(thr);
+  CHECK_IN(out);
+  TORCH_CHECK(frames.dtype() == torch::kUInt8, "frames must be uint8");
+  TORCH_CHECK(frames.dim() == 4 && frames.size(3) == 3,
+              "frames must be (B, H, W, 3)");
+  const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2);
+  TORCH_CHECK(B >= 1 && H >= 1 && W >= 1, "empty frame");
+  TORCH_CHECK(H * W * 3 < (1LL << 31) && B < 65536, "frame too large");
+  TORCH_CHECK(thr.dtype() == torch::kInt32 && thr.dim() == 2 &&
+                  thr.size(0) == B && thr.size(1) == 2,
+              "thr must be (B, 2) int32");
+  TORCH_CHECK(reach >= 0 && reach <= 32, "reach must be in [0, 32], got ",
+              reach);
+  TORCH_CHECK(out.dtype() == torch::kHalf || out.dtype() == torch::kFloat,
+              "out must be float16 or float32");
+  TORCH_CHECK(out.sizes() == frames.sizes(), "out has the wrong shape");
+  TORCH_CHECK(out.device() == frames.device() &&
+                  thr.device() == frames.device(),
+              "frames, thr and out must share a device");
+  const int rc = airtc_canny_hint(
+      frames.data_ptr<uint8_t>(), thr.data_ptr<int>(), out.data_ptr(),
+      out.dtype() == torch::kFloat ? 1 : 0, (int)B, (int)H, (int)W,
+      (int)reach, cur_stream());
+  TORCH_CHECK(rc == 0, "canny_hint: launch refused");
+  return out;
+}
+
 // --- software H.264 baseline-intra codec (h264sw.cpp) -----------------
 extern "C" {
 void* airtc_h264enc_create(int w, int h);
@@ -977,6 +1008,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("i420_to_rgb_u8", &i420_to_rgb_u8,
         "(B,3H/2,W) u8 I420 -> (B,H,W,3) u8 RGB",
         pybind11::arg("x"), pybind11::arg("out") = pybind11::none());
+  m.def("canny_hint", &canny_hint,
+        "(B,H,W,3) u8 RGB -> edge hint written into out (f16/f32); thr (B,2) "
+        "i32 read on the device, hysteresis bounded to `reach` steps",
+        pybind11::arg("frames"), pybind11::arg("thr"), pybind11::arg("reach"),
+        pybind11::arg("out"));
   m.def("conv2d_fp8", &conv2d_fp8,
         "fp8 e4m3 implicit-GEMM conv2d on the MX-scaled MFMA (NHWC)",
         pybind11::arg("x"), pybind11::arg("w_fp8"), pybind11::arg("dq"),

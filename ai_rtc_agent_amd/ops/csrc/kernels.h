@@ -44,6 +44,15 @@ void airtc_postprocess_i420(const uint16_t* in, uint8_t* out, int B, int H,
 // (B,3H/2,W) I420 -> (B,H,W,3) u8 RGB, chroma nearest-replicated
 void airtc_i420_to_rgb_u8(const uint8_t* in, uint8_t* out, int B, int H,
                           int W, hipStream_t s);
+// edge hint (canny.hip) -----------------------------------------------------
+// (B,H,W,3) u8 RGB -> (B,H,W,3) f16 (out_f32 == 0) or f32, three equal
+// channels, 1.0 on an edge: integer Canny with hysteresis bounded to `reach`
+// (0..32) 3x3 steps, one launch, no scratch. thr is (B,2) i32 (low, high)
+// per row, read on the device. Any H, W >= 1. Returns -1 and launches
+// nothing on a reach or grid out of range.
+int airtc_canny_hint(const uint8_t* in, const int* thr, void* out,
+                     int out_f32, int B, int H, int W, int reach,
+                     hipStream_t s);
 // fused LCM scheduler math (one kernel each; coefficients are per-batch-row
 // f32 arrays of B entries, per_b = elements per batch row)
 void airtc_sched_add_noise(const uint16_t* x0, const uint16_t* noise,

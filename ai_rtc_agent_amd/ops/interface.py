@@ -940,6 +940,166 @@ def postprocess_to_u8(img: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------
+# edge hint for ControlNet (ops/csrc/canny.hip)
+# ---------------------------------------------------------------------------
+# The operator, stated once; the HIP kernel and the torch path below are the
+# same integer arithmetic and agree bit for bit:
+#   Y  = (77R + 150G + 29B + 128) >> 8
+#   S  = (5x5 binomial [1,4,6,4,1]^2 of Y, taps clamped to the image, + 128) >> 8
+#   gx = (S[y-1,x+1] + 2S[y,x+1] + S[y+1,x+1]) - (S[y-1,x-1] + 2S[y,x-1] + S[y+1,x-1])
+#   gy = (S[y+1,x-1] + 2S[y+1,x] + S[y+1,x+1]) - (S[y-1,x-1] + 2S[y-1,x] + S[y-1,x+1])
+#        (taps clamped to the image);  M = |gx| + |gy| <= 2040
+#   non-maximum suppression in OpenCV's integer sectors, M outside the image
+#   counting as 0: ax = |gx|, ay = |gy| << 15, t22 = 13573 ax,
+#   t67 = t22 + (ax << 16);
+#     ay < t22: keep = M > M[y,x-1] and M >= M[y,x+1]
+#     ay > t67: keep = M > M[y-1,x] and M >= M[y+1,x]
+#     else, s = -1 if (gx ^ gy) < 0 else 1:
+#               keep = M > M[y-1,x-s] and M > M[y+1,x+s]
+#   cand = keep and M > low;  strong = keep and M > high
+#   E0 = strong;  `reach` times: E <- cand and (3x3 dilation of E)
+# The last step is where this differs from cv2.Canny, whose hysteresis
+# floods without bound: here a weak edge survives only within `reach` 3x3
+# steps of a strong pixel. That makes every pixel a function of the pixels
+# within Chebyshev distance reach + 4, which is what lets one kernel launch
+# with a fixed shape compute it inside a captured graph.
+
+CANNY_MAX_M = 2040
+CANNY_MAX_REACH = 32
+
+
+def check_canny_thresholds(low, high) -> tuple:
+    """(low, high) as ints, 0 <= low <= high <= 2040, else ValueError."""
+    try:
+        lo, hi = int(low), int(high)
+        ok = lo == low and hi == high
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"canny thresholds must be integers: {e}") from e
+    if not ok or isinstance(low, bool) or isinstance(high, bool):
+        raise ValueError(f"canny thresholds must be integers, got {low!r}, {high!r}")
+    if not 0 <= lo <= hi <= CANNY_MAX_M:
+        raise ValueError(
+            f"canny thresholds need 0 <= low <= high <= {CANNY_MAX_M}, "
+            f"got low={lo}, high={hi}")
+    return lo, hi
+
+
+def _taps(p: torch.Tensor, dy: int, dx: int, replicate: bool) -> torch.Tensor:
+    """p[..., y+dy, x+dx] over the whole (B,H,W) plane: coordinates clamped
+    to the image (replicate) or zero outside it."""
+    H, W = p.shape[-2], p.shape[-1]
+    if replicate:
+        iy = (torch.arange(H, device=p.device) + dy).clamp_(0, H - 1)
+        ix = (torch.arange(W, device=p.device) + dx).clamp_(0, W - 1)
+        return p[:, iy][:, :, ix]
+    q = F.pad(p, (1, 1, 1, 1))
+    return q[:, 1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
+
+
+def canny_hint_reference(frames_u8: torch.Tensor, thr: torch.Tensor,
+                         reach: int) -> torch.Tensor:
+    """The operator above in torch integer arithmetic: (B,H,W,3) u8 and
+    (B,2) int (low, high) -> (B,H,W) bool edge map."""
+    p = frames_u8.to(torch.int32)
+    sh = torch.bitwise_right_shift
+    Y = sh(77 * p[..., 0] + 150 * p[..., 1] + 29 * p[..., 2] + 128, 8)
+    k = (1, 4, 6, 4, 1)
+    acc = torch.zeros_like(Y)
+    for dy in range(-2, 3):
+        for dx in range(-2, 3):
+            acc += k[dy + 2] * k[dx + 2] * _taps(Y, dy, dx, True)
+    S = sh(acc + 128, 8)
+
+    def s(dy, dx):
+        return _taps(S, dy, dx, True)
+
+    gx = (s(-1, 1) + 2 * s(0, 1) + s(1, 1)) - (s(-1, -1) + 2 * s(0, -1) + s(1, -1))
+    gy = (s(1, -1) + 2 * s(1, 0) + s(1, 1)) - (s(-1, -1) + 2 * s(-1, 0) + s(-1, 1))
+    ax, ay = gx.abs(), gy.abs() << 15
+    M = ax + gy.abs()
+
+    def m(dy, dx):
+        return _taps(M, dy, dx, False)
+
+    t22 = ax * 13573
+    t67 = t22 + (ax << 16)
+    horiz = (M > m(0, -1)) & (M >= m(0, 1))
+    vert = (M > m(-1, 0)) & (M >= m(1, 0))
+    neg = (gx ^ gy) < 0  # s = -1
+    diag = torch.where(neg,
+                       (M > m(-1, 1)) & (M > m(1, -1)),
+                       (M > m(-1, -1)) & (M > m(1, 1)))
+    keep = torch.where(ay < t22, horiz, torch.where(ay > t67, vert, diag))
+    thr = thr.to(device=M.device, dtype=torch.int32)
+    cand = keep & (M > thr[:, 0].view(-1, 1, 1))
+    E = keep & (M > thr[:, 1].view(-1, 1, 1))
+    for _ in range(reach):
+        grown = cand & (F.max_pool2d(E.to(torch.float32), 3, 1, 1) > 0)
+        if torch.equal(grown, E):  # a fixed point: later passes change nothing
+            break
+        E = grown
+    return E
+
+
+def canny_hint(frames_u8: torch.Tensor, thr, reach: int = 16,
+               dtype: torch.dtype = torch.float16,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """Edge hint for an edge ControlNet: (B,H,W,3) u8 RGB -> (B,H,W,3) of
+    `dtype` (float16 or float32), the three channels equal, 1.0 on an edge
+    and 0.0 elsewhere. The operator is defined in the comment above; any
+    H, W >= 1.
+
+    thr: (B,2) int32 tensor of (low, high) per row on the frames' device, or
+    a pair of ints (validated, then broadcast into such a tensor). The
+    kernel reads the tensor from memory, so a captured graph follows
+    in-place writes to it. reach: 0..32 hysteresis steps, a launch constant.
+
+    GPU: ONE launch of canny_hint (ops/csrc/canny.hip) on the current
+    stream; the only allocation is `out` when it is not given, no sync.
+    CPU tensors and AIRTC_FORCE_EAGER=1 take canny_hint_reference."""
+    if frames_u8.dtype != torch.uint8:
+        raise TypeError("canny_hint takes uint8 frames")
+    if frames_u8.dim() != 4 or frames_u8.shape[-1] != 3 or frames_u8.numel() == 0:
+        raise ValueError(
+            f"canny_hint needs frames (B,H,W,3), got {tuple(frames_u8.shape)}")
+    if dtype not in (torch.float16, torch.float32):
+        raise TypeError(f"canny_hint writes float16 or float32, got {dtype}")
+    if isinstance(reach, bool) or not isinstance(reach, int) \
+            or not 0 <= reach <= CANNY_MAX_REACH:
+        raise ValueError(
+            f"reach must be an int in [0, {CANNY_MAX_REACH}], got {reach!r}")
+    B = frames_u8.shape[0]
+    if not isinstance(thr, torch.Tensor):
+        if len(thr) != 2:
+            raise ValueError("thr must be a (low, high) pair or a (B,2) tensor")
+        lo, hi = check_canny_thresholds(*thr)
+        thr = torch.tensor([[lo, hi]] * B, dtype=torch.int32,
+                           device=frames_u8.device)
+    if thr.dtype != torch.int32 or tuple(thr.shape) != (B, 2) \
+            or thr.device != frames_u8.device:
+        raise ValueError(
+            f"thr must be a ({B}, 2) int32 tensor on {frames_u8.device}, got "
+            f"{thr.dtype} {tuple(thr.shape)} on {thr.device}")
+    if out is not None and (
+            out.dtype != dtype or out.shape != frames_u8.shape
+            or out.device != frames_u8.device or not out.is_contiguous()):
+        raise ValueError(
+            f"out must be a contiguous {dtype} {tuple(frames_u8.shape)} tensor "
+            f"on {frames_u8.device}")
+    if _on_kernel(frames_u8):
+        if out is None:
+            out = torch.empty(frames_u8.shape, dtype=dtype, device=frames_u8.device)
+        return _require_ext().canny_hint(
+            frames_u8.contiguous(), thr.contiguous(), reach, out)
+    E = canny_hint_reference(frames_u8, thr, reach)
+    res = E.unsqueeze(-1).expand(-1, -1, -1, 3).to(dtype)
+    if out is not None:
+        out.copy_(res)
+        return out
+    return res.contiguous()
+
+
+# ---------------------------------------------------------------------------
 # YUV 4:2:0 frames (ops/csrc/color.hip)
 # ---------------------------------------------------------------------------
 # The frame format, stated once for the whole package:

@@ -50,6 +50,9 @@ class SlotProxy:
     def update_t_index_list(self, t: list) -> None:
         self._owner.base.update_t_index_list(t, slot=self.slot)
 
+    def update_canny(self, low=None, high=None) -> None:
+        self._owner.base.update_canny(low, high, slot=self.slot)
+
     def stats(self) -> dict:
         return self._owner.stats()
 
@@ -87,6 +90,9 @@ class BatchedPipeline:
 
     def update_t_index_list(self, t: list) -> None:
         self.base.update_t_index_list(t)
+
+    def update_canny(self, low=None, high=None) -> None:
+        self.base.update_canny(low, high)
 
     # -- slot lifecycle --------------------------------------------------
     def acquire(self, stream_id: str) -> Optional[SlotProxy]:

@@ -70,6 +70,10 @@ class StreamDiffusionPipeline:
                             slot: Optional[int] = None) -> None:
         self.engine.update_t_index_list(list(t_index_list), slot=slot)
 
+    def update_canny(self, low: Optional[int] = None, high: Optional[int] = None,
+                     slot: Optional[int] = None) -> None:
+        self.engine.update_canny(low, high, slot=slot)
+
     def reset_slot(self, slot: int) -> None:
         self.engine.reset_slot(slot)
 
