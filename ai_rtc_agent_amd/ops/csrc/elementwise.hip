@@ -13,11 +13,16 @@
 #define EW_MAX_BLOCKS 2048
 
 // ---------------------------------------------------------------------------
-// u8 RGB -> f16 in [-1, 1]    (n = total element count, multiple of 8)
+// u8 RGB -> f16 in [-1, 1]    (n = total element count, any; the last n % 8
+// elements are written one by one by the first lanes of block 0, same launch)
 // ---------------------------------------------------------------------------
 __global__ void preprocess_u8_kernel(const uint8_t* __restrict__ in,
-                                     f16* __restrict__ out, long n8) {
+                                     f16* __restrict__ out, long n8, int tail) {
   const float inv = 1.0f / 127.5f;
+  if (blockIdx.x == 0 && (int)threadIdx.x < tail) {
+    const long t = n8 * 8 + threadIdx.x;
+    out[t] = (f16)((float)in[t] * inv - 1.0f);
+  }
   for (long i = blockIdx.x * blockDim.x + threadIdx.x; i < n8;
        i += gridDim.x * blockDim.x) {
     // 8 u8 in, 8 f16 out per lane
@@ -32,37 +37,50 @@ __global__ void preprocess_u8_kernel(const uint8_t* __restrict__ in,
 
 extern "C" void airtc_preprocess_u8(const uint8_t* in, uint16_t* out, long n,
                                     hipStream_t s) {
+  if (n <= 0) return;
   long n8 = n / 8;
   int blocks = (int)min((long)EW_MAX_BLOCKS, (n8 + EW_BLOCK - 1) / EW_BLOCK);
+  if (blocks < 1) blocks = 1;  // n < 8: the tail lanes alone
   hipLaunchKernelGGL(preprocess_u8_kernel, dim3(blocks), dim3(EW_BLOCK), 0, s,
-                     in, reinterpret_cast<f16*>(out), n8);
+                     in, reinterpret_cast<f16*>(out), n8, (int)(n - n8 * 8));
 }
 
 // ---------------------------------------------------------------------------
 // f16 in [-1,1] -> u8 with round+clamp (reference lib/pipeline.py:74)
 // ---------------------------------------------------------------------------
+__device__ __forceinline__ uint8_t post_u8(f16 x) {
+  const float f = ((float)x + 1.0f) * 127.5f;
+  return (uint8_t)min(255.0f, max(0.0f, nearbyintf(f)));
+}
+
+// n any: the last n % 8 elements go one by one, as in preprocess_u8_kernel
 __global__ void postprocess_u8_kernel(const f16* __restrict__ in,
-                                      uint8_t* __restrict__ out, long n8) {
+                                      uint8_t* __restrict__ out, long n8,
+                                      int tail) {
+  if (blockIdx.x == 0 && (int)threadIdx.x < tail) {
+    const long t = n8 * 8 + threadIdx.x;
+    out[t] = post_u8(in[t]);
+  }
   for (long i = blockIdx.x * blockDim.x + threadIdx.x; i < n8;
        i += gridDim.x * blockDim.x) {
     f16x8 v = reinterpret_cast<const f16x8*>(in)[i];
     uint2 packed;
     uint8_t* b = reinterpret_cast<uint8_t*>(&packed);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float f = ((float)v[j] + 1.0f) * 127.5f;
-      b[j] = (uint8_t)min(255.0f, max(0.0f, nearbyintf(f)));
-    }
+    for (int j = 0; j < 8; ++j) b[j] = post_u8(v[j]);
     reinterpret_cast<uint2*>(out)[i] = packed;
   }
 }
 
 extern "C" void airtc_postprocess_u8(const uint16_t* in, uint8_t* out, long n,
                                      hipStream_t s) {
+  if (n <= 0) return;
   long n8 = n / 8;
   int blocks = (int)min((long)EW_MAX_BLOCKS, (n8 + EW_BLOCK - 1) / EW_BLOCK);
+  if (blocks < 1) blocks = 1;  // n < 8: the tail lanes alone
   hipLaunchKernelGGL(postprocess_u8_kernel, dim3(blocks), dim3(EW_BLOCK), 0, s,
-                     reinterpret_cast<const f16*>(in), out, n8);
+                     reinterpret_cast<const f16*>(in), out, n8,
+                     (int)(n - n8 * 8));
 }
 
 // ---------------------------------------------------------------------------

@@ -295,9 +295,15 @@ torch::Tensor group_norm_silu(torch::Tensor x, int64_t groups,
 torch::Tensor layer_norm(torch::Tensor x, torch::Tensor gamma,
                          torch::Tensor beta, double eps) {
   CHECK_IN(x);
+  TORCH_CHECK(x.dtype() == torch::kHalf, "layer_norm: x must be float16");
   const int C = x.size(-1);
+  TORCH_CHECK(C > 0 && C % 8 == 0,
+              "layer_norm: the kernel reads 8 channels per lane, C = ", C);
+  TORCH_CHECK(gamma.numel() == C && beta.numel() == C,
+              "layer_norm: gamma/beta must hold C values");
   const long rows = x.numel() / C;
   auto out = torch::empty_like(x);
+  if (rows == 0) return out;
   airtc_layer_norm(h_ptr(x), gamma.data_ptr<float>(), beta.data_ptr<float>(),
                    h_ptr_mut(out), rows, C, (float)eps, cur_stream());
   return out;
@@ -307,14 +313,28 @@ torch::Tensor attention_bhlc(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                              int64_t heads, double scale) {
   // q/k/v: (B, L, C) with unit channel stride; row/batch strides are free so
   // chunk() views of a fused QKV projection run zero-copy.
-  TORCH_CHECK(q.is_cuda() && q.stride(2) == 1, "q: unit channel stride");
+  TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda(), "q/k/v must be on GPU");
+  TORCH_CHECK(q.dim() == 3 && k.dim() == 3 && v.dim() == 3, "q/k/v: (B, L, C)");
+  TORCH_CHECK(q.dtype() == torch::kHalf && k.dtype() == torch::kHalf &&
+                  v.dtype() == torch::kHalf, "q/k/v must be float16");
+  TORCH_CHECK(q.stride(2) == 1, "q: unit channel stride");
   TORCH_CHECK(k.stride(2) == 1 && v.stride(2) == 1, "k/v: unit channel stride");
-  TORCH_CHECK(k.strides() == v.strides(), "k/v must share layout");
+  TORCH_CHECK(k.sizes() == v.sizes() && k.strides() == v.strides(),
+              "k/v must share layout");
   const int B = q.size(0), Lq = q.size(1), C = q.size(2);
   const int Lk = k.size(1), Ck = k.size(2);
+  TORCH_CHECK(heads > 0 && C % heads == 0, "channels must split into heads");
   const int d = C / (int)heads;
-  TORCH_CHECK(Ck == C, "q/k channel mismatch");
-  TORCH_CHECK(d % 32 == 0 && d <= 160, "head_dim must be padded to one of 32/64/96/128/160");
+  TORCH_CHECK(Ck == C && k.size(0) == B, "q/k batch or channel mismatch");
+  TORCH_CHECK(d > 0 && d % 32 == 0 && d <= 160, "head_dim must be padded to one of 32/64/96/128/160");
+  TORCH_CHECK(Lq > 0 && Lk > 0 && B > 0, "attention needs non-empty q and k");
+  // the kernel reads rows with 16-byte loads: every row must start on one
+  TORCH_CHECK(q.stride(1) % 8 == 0 && k.stride(1) % 8 == 0 &&
+                  q.stride(0) % 8 == 0 && k.stride(0) % 8 == 0,
+              "q/k/v row and batch strides must be multiples of 8 elements");
+  TORCH_CHECK(aligned16(q.data_ptr()) && aligned16(k.data_ptr()) &&
+                  aligned16(v.data_ptr()),
+              "q/k/v must start on a 16-byte boundary");
   auto out = torch::empty({B, Lq, C}, q.options());
   airtc_attention(h_ptr(q), h_ptr(k), h_ptr(v), h_ptr_mut(out), B, (int)heads,
                   Lq, Lk, d, q.stride(0), d, q.stride(1), k.stride(0), d,
@@ -331,6 +351,10 @@ torch::Tensor silu(torch::Tensor x) {
 
 torch::Tensor geglu(torch::Tensor x) {
   CHECK_IN(x);
+  TORCH_CHECK(x.dtype() == torch::kHalf, "geglu: x must be float16");
+  TORCH_CHECK(x.size(-1) % 16 == 0,
+              "geglu: the kernel reads 8 channels per lane of each half, the "
+              "last dimension must be a multiple of 16, got ", x.size(-1));
   const long inner = x.size(-1) / 2;
   const long rows = x.numel() / (2 * inner);
   auto sizes = x.sizes().vec();
@@ -343,7 +367,13 @@ torch::Tensor geglu(torch::Tensor x) {
 torch::Tensor add_act(torch::Tensor a, torch::Tensor b, int64_t act) {
   CHECK_IN(a);
   CHECK_IN(b);
+  TORCH_CHECK(a.dtype() == torch::kHalf && b.dtype() == torch::kHalf,
+              "add_act: a and b must be float16");
+  TORCH_CHECK(a.numel() == b.numel(), "add_act: a has ", a.numel(),
+              " elements, b ", b.numel());
+  TORCH_CHECK(a.numel() % 8 == 0, "add_act: numel must be a multiple of 8");
   auto out = torch::empty_like(a);
+  if (a.numel() == 0) return out;
   airtc_add_act_f16(h_ptr(a), h_ptr(b), h_ptr_mut(out), a.numel(), (int)act,
                     cur_stream());
   return out;

@@ -5,7 +5,8 @@
 // One workgroup per (batch, group); two passes over the group's slice
 // (sum/sumsq reduce, then normalise+affine+activation) with half2 loads.
 //
-// layer_norm: one wave per row (transformer blocks), f16x8 loads, f32 stats.
+// layer_norm: one wave per row (transformer blocks), f16x8 loads, two-pass
+// f32 stats on deviations from the row's first element.
 
 #include <stdlib.h>
 
@@ -75,7 +76,9 @@ __device__ __forceinline__ void gn_fold_partials(const float* w, int npart,
   for (int i = 0; i < npart; ++i) { s0 += w[2 * i]; s1 += w[2 * i + 1]; }
   const float mean = s0 / n;
   *mean_out = mean;
-  *rstd_out = rsqrtf(s1 / n - mean * mean + eps);
+  // one-pass variance: cancellation can take it below 0 on a near-constant
+  // group, and rsqrtf of a negative argument is NaN
+  *rstd_out = rsqrtf(fmaxf(s1 / n - mean * mean, 0.f) + eps);
 }
 
 // Q8: the apply pass writes OCP e4m3 CODES (q = clamp(act(gn(x)) * inv_sa,
@@ -428,6 +431,10 @@ extern "C" void airtc_group_norm(const uint16_t* x, const float* part,
 // ---------------------------------------------------------------------------
 // LayerNorm: rows x C, one wave per row (C % 8 == 0)
 // ---------------------------------------------------------------------------
+// NV > 0: the row fits NV f16x8 per lane (C8 <= NV * 64) and is read ONCE
+// into registers; all three sweeps below run on them. NV == 0: any C8, the
+// row is re-read from cache for each sweep.
+template <int NV>
 __global__ void layer_norm_kernel(const f16* __restrict__ x,
                                   const float* __restrict__ gamma,
                                   const float* __restrict__ beta,
@@ -437,31 +444,63 @@ __global__ void layer_norm_kernel(const f16* __restrict__ x,
   const long row = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= rows) return;
   const f16x8* xr = reinterpret_cast<const f16x8*>(x) + row * C8;
-
-  float sum = 0.f, sumsq = 0.f;
-  for (int i = lane; i < C8; i += WAVE) {
-    f16x8 v = xr[i];
+  constexpr int NR = NV > 0 ? NV : 1;
+  f16x8 reg[NR];
+  if (NV > 0) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float f = (float)v[j];
-      sum += f;
-      sumsq += f * f;
+    for (int k = 0; k < NR; ++k) {
+      const int i = lane + k * WAVE;
+      if (i < C8) reg[k] = xr[i];
     }
   }
+  // body(i, v) over this lane's vectors of the row
+  auto sweep = [&](auto body) {
+    if constexpr (NV > 0) {
+#pragma unroll
+      for (int k = 0; k < NR; ++k) {
+        const int i = lane + k * WAVE;
+        if (i < C8) body(i, reg[k]);
+      }
+    } else {
+      for (int i = lane; i < C8; i += WAVE) body(i, xr[i]);
+    }
+  };
+
+  // Statistics on deviations from the row's first element: a difference of
+  // two f16 values of similar magnitude is exact in f32 (otherwise it is one
+  // f32 rounding), so a row far from zero (mean 64, std 0.25) keeps every
+  // variance bit that sumsq/n - mean^2 cancels away.
+  // Mean of the deviations first, then the centred sum of squares in a
+  // second sweep.
+  const float pivot = (float)x[row * C8 * 8];
+  float sum = 0.f;
+  sweep([&](int, const f16x8 v) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sum += (float)v[j] - pivot;
+  });
   sum = wave_reduce(sum, SumOp());
+  const float n = (float)C8 * 8.0f;
+  const float dmean = sum / n;
+  float sumsq = 0.f;
+  sweep([&](int, const f16x8 v) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float c = ((float)v[j] - pivot) - dmean;
+      sumsq += c * c;
+    }
+  });
   sumsq = wave_reduce(sumsq, SumOp());
-  float n = (float)C8 * 8.0f;
-  float mean = sum / n;
-  float rstd = rsqrtf(sumsq / n - mean * mean + eps);
+  const float rstd = rsqrtf(fmaxf(sumsq / n, 0.f) + eps);
 
   f16x8* orow = reinterpret_cast<f16x8*>(out) + row * C8;
-  for (int i = lane; i < C8; i += WAVE) {
-    f16x8 v = xr[i];
+  sweep([&](int i, const f16x8 v) {
+    f16x8 o;
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-      v[j] = (f16)(((float)v[j] - mean) * rstd * gamma[i * 8 + j] + beta[i * 8 + j]);
-    orow[i] = v;
-  }
+      o[j] = (f16)((((float)v[j] - pivot) - dmean) * rstd * gamma[i * 8 + j] +
+                   beta[i * 8 + j]);
+    orow[i] = o;
+  });
 }
 
 extern "C" void airtc_layer_norm(const uint16_t* x, const float* gamma,
@@ -469,8 +508,17 @@ extern "C" void airtc_layer_norm(const uint16_t* x, const float* gamma,
                                  int C, float eps, hipStream_t s) {
   int waves_per_block = 4;
   long blocks = (rows + waves_per_block - 1) / waves_per_block;
-  hipLaunchKernelGGL(layer_norm_kernel, dim3((uint32_t)blocks),
-                     dim3(waves_per_block * WAVE), 0, s,
-                     reinterpret_cast<const f16*>(x), gamma, beta,
-                     reinterpret_cast<f16*>(out), rows, C / 8, eps);
+  const int C8 = C / 8;
+#define LN_LAUNCH(NV)                                                      \
+  hipLaunchKernelGGL(layer_norm_kernel<NV>, dim3((uint32_t)blocks),        \
+                     dim3(waves_per_block * WAVE), 0, s,                   \
+                     reinterpret_cast<const f16*>(x), gamma, beta,         \
+                     reinterpret_cast<f16*>(out), rows, C8, eps)
+  // C <= 2048: the row stays in registers (1..4 vectors per lane)
+  if (C8 <= 1 * WAVE) LN_LAUNCH(1);
+  else if (C8 <= 2 * WAVE) LN_LAUNCH(2);
+  else if (C8 <= 3 * WAVE) LN_LAUNCH(3);
+  else if (C8 <= 4 * WAVE) LN_LAUNCH(4);
+  else LN_LAUNCH(0);
+#undef LN_LAUNCH
 }

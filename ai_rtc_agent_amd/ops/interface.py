@@ -524,7 +524,8 @@ def group_norm_silu_nhwc(
 def layer_norm(
     x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5
 ) -> torch.Tensor:
-    if _use_hip(x):
+    # the kernel reads 8 channels per lane; other widths take the torch path
+    if _use_hip(x) and x.shape[-1] % 8 == 0:
         ext = _require_ext()
         g32 = _cached(gamma, "_airtc_g32", lambda: gamma.detach().float().contiguous())
         b32 = _cached(beta, "_airtc_b32", lambda: beta.detach().float().contiguous())
@@ -665,7 +666,7 @@ def _linear_residual_lt(x, weight, bias, residual):
 
 def geglu(x: torch.Tensor) -> torch.Tensor:
     """GEGLU activation: split last dim, a * gelu(b). GPU: fused kernel."""
-    if _use_hip(x):
+    if _use_hip(x) and x.shape[-1] % 16 == 0:  # inner % 8: 16 B per lane
         return _require_ext().geglu(x)
     a, b = x.chunk(2, dim=-1)
     return (a.float() * F.gelu(b.float())).to(x.dtype)
