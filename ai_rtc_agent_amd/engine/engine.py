@@ -363,17 +363,8 @@ class StreamDiffusionEngine:
         transforms (conv GEMM layouts, fused QKV, f32 bias copies), re-sync
         replicas, and force a graph re-capture."""
         for module in (self.unet, self.vae, self.controlnet):
-            if module is None:
-                continue
-            for m in module.modules():
-                for attr in ("_wqkv", "_wkv", "_wq", "_wout"):
-                    if hasattr(m, attr):
-                        delattr(m, attr)
-                for t in list(m.parameters(recurse=False)):
-                    for attr in ("_airtc_wperm", "_airtc_b32", "_airtc_g32", "_airtc_w16", "_airtc_wpad32", "_airtc_wfp8", "_airtc_wdq",
-                                 "_airtc_wtail", "_airtc_btail", "_airtc_wtiny"):
-                        if hasattr(t, attr):
-                            delattr(t, attr)
+            if module is not None:
+                ops.drop_weight_caches(module)
         from ..parallel.collectives import broadcast_engine_weights
 
         broadcast_engine_weights(self)  # no-op at world_size 1

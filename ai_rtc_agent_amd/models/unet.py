@@ -290,11 +290,9 @@ class CrossAttention(nn.Module):
         return wp.reshape(self.heads * self.dpad, src)
 
     def _cached_w(self, name: str, ref: torch.Tensor, build) -> torch.Tensor:
-        w = getattr(self, name, None)
-        if w is None or w.device != ref.device or w.dtype != ref.dtype:
-            w = build().detach().to(ref.device, ref.dtype)
-            setattr(self, name, w)
-        return w
+        return ops.weight_cache(
+            self, name, lambda: build().detach().to(ref.device, ref.dtype),
+            key=(ref.device, ref.dtype))
 
     def compute_kv(self, ctx: torch.Tensor) -> torch.Tensor:
         """Fused K|V projection of a context. The engine calls this at

@@ -47,6 +47,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "kernels.h"
 
 #define BN 64
 
@@ -690,25 +691,23 @@ extern "C" int airtc_conv2d_stats_nchunk(int B, int HO, int WO, int OC, int IC,
   return fin_stats_plan(HO * WO, OC, G, &p) ? p.nchunk : 0;
 }
 
-extern "C" int airtc_conv2d_mfma(const uint16_t* x, const uint16_t* w,
-                                 const float* bias, const uint16_t* cbias,
-                                 const uint16_t* residual, uint16_t* out,
-                                 float* ws, int B, int H, int W, int IC,
-                                 int HO, int WO, int OC, int R, int S,
-                                 int stride, int pad, int act, int path,
-                                 const float* in_aff, int in_act,
-                                 float* gn_part, int gn_groups,
-                                 const uint16_t* x2, int IC2, int up,
-                                 hipStream_t s) {
-  // H, W: the extents the conv sees (the upsampled ones when up == 1);
+extern "C" int airtc_conv2d_mfma(const AirtcConvArgs* a, hipStream_t s) {
+  const int B = a->B, H = a->H, W = a->W, IC = a->IC, HO = a->HO, WO = a->WO,
+            OC = a->OC, R = a->R, S = a->S, stride = a->stride, pad = a->pad,
+            act = a->act, path = a->path, in_act = a->in_act, IC2 = a->IC2,
+            up = a->up, gn_groups = a->gn_groups;
+  const float* bias = a->bias;
+  const float* in_aff = a->in_aff;
+  float* ws = a->ws;
+  float* gn_part = a->gn_part;
   // w rows are R*S*IC + IC2 long
   const int K = R * S * IC + IC2;
-  const f16* xp = reinterpret_cast<const f16*>(x);
-  const f16* x2p = reinterpret_cast<const f16*>(x2);
-  const f16* wp = reinterpret_cast<const f16*>(w);
-  const f16* cb = reinterpret_cast<const f16*>(cbias);
-  const f16* res = reinterpret_cast<const f16*>(residual);
-  f16* op = reinterpret_cast<f16*>(out);
+  const f16* xp = reinterpret_cast<const f16*>(a->x);
+  const f16* x2p = reinterpret_cast<const f16*>(a->x2);
+  const f16* wp = reinterpret_cast<const f16*>(a->w);
+  const f16* cb = reinterpret_cast<const f16*>(a->cbias);
+  const f16* res = reinterpret_cast<const f16*>(a->residual);
+  f16* op = reinterpret_cast<f16*>(a->out);
   const int M = HO * WO;
 
   const int splitk = path > 0 ? path : -path;
@@ -781,56 +780,44 @@ extern "C" int airtc_conv2d_tinyic_ok(int IC, int R, int S) {
   return IC <= 4 && R * S * IC <= TINY_TK;
 }
 
-// wt: (TINY_TK, OC) f32, row k = weight column k of the (OC, R*S*IC) GEMM
-// layout, rows past K zero
-extern "C" void airtc_conv2d_tinyic(const uint16_t* x, const float* wt,
-                                    const float* bias, const uint16_t* cbias,
-                                    const uint16_t* residual, uint16_t* out,
-                                    int B, int H, int W, int IC, int HO,
-                                    int WO, int OC, int R, int S, int stride,
-                                    int pad, int act, hipStream_t s) {
-  const long pix = (long)B * HO * WO;
-  const int tiles = ceil_div(OC, 64);
+extern "C" void airtc_conv2d_tinyic(const AirtcConvArgs* a, hipStream_t s) {
+  const long pix = (long)a->B * a->HO * a->WO;
+  const int tiles = ceil_div(a->OC, 64);
   // largest pixel chunk that still gives >= 512 blocks (2 per CU), 8..64
   int ppb = TINY_PPB;
   while (ppb > 8 && ((pix + ppb - 1) / ppb) * tiles < 512) ppb >>= 1;
   dim3 grid((uint32_t)((pix + ppb - 1) / ppb), tiles);
   hipLaunchKernelGGL(conv2d_tinyic_kernel, grid, dim3(256), 0, s,
-                     reinterpret_cast<const f16*>(x), wt, bias,
-                     reinterpret_cast<const f16*>(cbias),
-                     reinterpret_cast<const f16*>(residual),
-                     reinterpret_cast<f16*>(out), H, W, IC, HO, WO, OC, S,
-                     stride, pad, act, R * S * IC, pix, ppb);
+                     reinterpret_cast<const f16*>(a->x),
+                     reinterpret_cast<const float*>(a->w), a->bias,
+                     reinterpret_cast<const f16*>(a->cbias),
+                     reinterpret_cast<const f16*>(a->residual),
+                     reinterpret_cast<f16*>(a->out), a->H, a->W, a->IC, a->HO,
+                     a->WO, a->OC, a->S, a->stride, a->pad, a->act,
+                     a->R * a->S * a->IC, pix, ppb);
 }
 
-extern "C" void airtc_conv2d_direct(const uint16_t* x, const uint16_t* w,
-                                    const float* bias, const uint16_t* cbias,
-                                    const uint16_t* residual, uint16_t* out,
-                                    int B, int H, int W, int IC, int HO,
-                                    int WO, int OC, int R, int S, int stride,
-                                    int pad, int act, const float* in_aff,
-                                    int in_act, hipStream_t s) {
-  const int K = R * S * IC;
+extern "C" void airtc_conv2d_direct(const AirtcConvArgs* a, hipStream_t s) {
+  const f16* x = reinterpret_cast<const f16*>(a->x);
+  const f16* w = reinterpret_cast<const f16*>(a->w);
+  const f16* cb = reinterpret_cast<const f16*>(a->cbias);
+  const f16* res = reinterpret_cast<const f16*>(a->residual);
+  f16* out = reinterpret_cast<f16*>(a->out);
+  const int K = a->R * a->S * a->IC;
+  const long pix = (long)a->B * a->HO * a->WO;
   if (K <= SMALLIC_MAX_K) {
-    long pix = (long)B * HO * WO;
     dim3 grid((uint32_t)min((long)4096, (pix + 255) / 256),
-              ceil_div(OC, OCT));
-    hipLaunchKernelGGL(conv2d_smallic_kernel, grid, dim3(256), 0, s,
-                       reinterpret_cast<const f16*>(x),
-                       reinterpret_cast<const f16*>(w), bias,
-                       reinterpret_cast<const f16*>(cbias),
-                       reinterpret_cast<const f16*>(residual),
-                       reinterpret_cast<f16*>(out), H, W, IC, HO, WO, OC, R,
-                       S, stride, pad, act, K, pix, in_aff, in_act);
+              ceil_div(a->OC, OCT));
+    hipLaunchKernelGGL(conv2d_smallic_kernel, grid, dim3(256), 0, s, x, w,
+                       a->bias, cb, res, out, a->H, a->W, a->IC, a->HO, a->WO,
+                       a->OC, a->R, a->S, a->stride, a->pad, a->act, K, pix,
+                       a->in_aff, a->in_act);
     return;
   }
-  long total = (long)B * HO * WO * OC;
+  long total = pix * a->OC;
   int blocks = (int)min((long)4096, (total + 255) / 256);
-  hipLaunchKernelGGL(conv2d_direct_kernel, dim3(blocks), dim3(256), 0, s,
-                     reinterpret_cast<const f16*>(x),
-                     reinterpret_cast<const f16*>(w), bias,
-                     reinterpret_cast<const f16*>(cbias),
-                     reinterpret_cast<const f16*>(residual),
-                     reinterpret_cast<f16*>(out), H, W, IC, HO, WO, OC, R, S,
-                     stride, pad, act, K, total, in_aff, in_act);
+  hipLaunchKernelGGL(conv2d_direct_kernel, dim3(blocks), dim3(256), 0, s, x, w,
+                     a->bias, cb, res, out, a->H, a->W, a->IC, a->HO, a->WO,
+                     a->OC, a->R, a->S, a->stride, a->pad, a->act, K, total,
+                     a->in_aff, a->in_act);
 }

@@ -27,6 +27,7 @@
 // reused unchanged.
 
 #include "common.h"
+#include "kernels.h"
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
@@ -374,17 +375,21 @@ __global__ void conv_splitk_finalize_fp8(const float* __restrict__ ws,
   }
 }
 
-extern "C" void airtc_conv2d_fp8_mfma(
-    const uint16_t* x, const uint8_t* w_fp8, const float* dq,
-    const float* bias, const uint16_t* cbias, const uint16_t* residual,
-    uint16_t* out, float* ws, int B, int H, int W, int IC, int HO, int WO,
-    int OC, int R, int S, int stride, int pad, int act, int path,
-    const float* in_aff, int in_act, float a_scale, int x_is_q8,
-    uint8_t* out_q8, float out_inv, hipStream_t s) {
+extern "C" void airtc_conv2d_fp8_mfma(const AirtcConvArgs* a, const float* dq,
+                                      float a_scale, int x_is_q8,
+                                      uint8_t* out_q8, float out_inv,
+                                      hipStream_t s) {
+  const int B = a->B, H = a->H, W = a->W, IC = a->IC, HO = a->HO, WO = a->WO,
+            OC = a->OC, R = a->R, S = a->S, stride = a->stride, pad = a->pad,
+            act = a->act, path = a->path, in_act = a->in_act;
+  const float* bias = a->bias;
+  const float* in_aff = a->in_aff;
+  float* ws = a->ws;
+  const uint8_t* w_fp8 = reinterpret_cast<const uint8_t*>(a->w);
   const int K = R * S * IC;
-  const f16* cb = reinterpret_cast<const f16*>(cbias);
-  const f16* res = reinterpret_cast<const f16*>(residual);
-  f16* op = reinterpret_cast<f16*>(out);
+  const f16* cb = reinterpret_cast<const f16*>(a->cbias);
+  const f16* res = reinterpret_cast<const f16*>(a->residual);
+  f16* op = reinterpret_cast<f16*>(a->out);
   const int M = HO * WO;
 
   const int splitk = path > 0 ? path : -path;
@@ -399,11 +404,11 @@ extern "C" void airtc_conv2d_fp8_mfma(
                      OC, R, S, stride, pad, act, K, splitk, in_aff, in_act,   \
                      a_scale, splitk == 1 ? out_q8 : nullptr, out_inv)
   if (x_is_q8) {
-    const uint8_t* xq = reinterpret_cast<const uint8_t*>(x);
+    const uint8_t* xq = reinterpret_cast<const uint8_t*>(a->x);
     if (path > 0) FP8_LAUNCH(4, uint8_t, xq);
     else FP8_LAUNCH(2, uint8_t, xq);
   } else {
-    const f16* xp = reinterpret_cast<const f16*>(x);
+    const f16* xp = reinterpret_cast<const f16*>(a->x);
     if (path > 0) FP8_LAUNCH(4, f16, xp);
     else FP8_LAUNCH(2, f16, xp);
   }

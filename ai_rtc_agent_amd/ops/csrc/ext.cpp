@@ -7,6 +7,9 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
+#include <algorithm>
+#include <limits>
+
 #include "kernels.h"
 
 #define CHECK_IN(x)                                                     \
@@ -28,205 +31,303 @@ uint16_t* h_ptr_mut(torch::Tensor& t) {
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-// stats_groups > 0 asks the split-K finalize for GroupNorm partials of the
-// output (kernels.h layout); *gn_part stays undefined when the shape takes
-// no finalize pass or the finalize cannot produce them.
-// x2: optional second K segment (B, HO, WO, IC2), w_perm then (OC, R*S*IC +
-// IC2); upsample2x: x is read through nearest-2x addressing (MFMA path only)
-torch::Tensor conv2d_impl(torch::Tensor x, torch::Tensor w_perm,
-                          c10::optional<torch::Tensor> bias,
-                          c10::optional<torch::Tensor> cbias,
-                          c10::optional<torch::Tensor> residual, int64_t R,
-                          int64_t S, int64_t stride, int64_t pad, int64_t act,
-                          c10::optional<torch::Tensor> in_affine,
-                          int64_t in_act, int64_t stats_groups,
-                          torch::Tensor* gn_part,
-                          c10::optional<torch::Tensor> x2, bool upsample2x) {
-  CHECK_IN(x);
-  CHECK_IN(w_perm);
-  TORCH_CHECK(x.dtype() == torch::kHalf && w_perm.dtype() == torch::kHalf);
-  TORCH_CHECK(x.dim() == 4 && w_perm.dim() == 2);
-  const int up = upsample2x ? 1 : 0;
-  const int B = x.size(0), IC = x.size(3);
-  const int H = (int)x.size(1) << up, W = (int)x.size(2) << up;
-  const int OC = w_perm.size(0);
-  const int HO = (H + 2 * (int)pad - (int)R) / (int)stride + 1;
-  const int WO = (W + 2 * (int)pad - (int)S) / (int)stride + 1;
-  auto out = torch::empty({B, HO, WO, OC}, x.options());
-  const float* bp = nullptr;
-  if (bias.has_value()) {
-    TORCH_CHECK(bias->dtype() == torch::kFloat && bias->is_contiguous());
-    bp = bias->data_ptr<float>();
-  }
-  const uint16_t* cb = nullptr;
-  if (cbias.has_value()) {
-    CHECK_IN((*cbias));
-    TORCH_CHECK(cbias->dtype() == torch::kHalf);
-    cb = h_ptr(*cbias);
-  }
-  const uint16_t* res = nullptr;
-  if (residual.has_value()) {
-    CHECK_IN((*residual));
-    TORCH_CHECK(residual->dtype() == torch::kHalf);
-    TORCH_CHECK(residual->numel() == out.numel(), "residual shape mismatch");
-    res = h_ptr(*residual);
-  }
-  const float* aff = nullptr;
-  if (in_affine.has_value()) {
-    CHECK_IN((*in_affine));
-    TORCH_CHECK(in_affine->dtype() == torch::kFloat &&
-                    in_affine->numel() == (long)B * IC * 2,
-                "in_affine must be (B, IC, 2) f32");
-    aff = in_affine->data_ptr<float>();
-  }
-  const uint16_t* x2p = nullptr;
-  int IC2 = 0;
-  if (x2.has_value()) {
-    CHECK_IN((*x2));
-    TORCH_CHECK(x2->dtype() == torch::kHalf && x2->dim() == 4);
-    IC2 = x2->size(3);
-    TORCH_CHECK(x2->size(0) == B && x2->size(1) == HO && x2->size(2) == WO,
-                "x2 must be (B, HO, WO, IC2)");
-    TORCH_CHECK(stride == 1 && IC2 > 0 && IC2 % 32 == 0,
-                "x2 needs stride 1 and IC2 % 32 == 0");
-    // the kernel offsets x2 per batch in 32 bits
-    TORCH_CHECK((long)HO * WO * IC2 < (1L << 31), "x2 too large");
-    x2p = h_ptr(*x2);
-  }
-  TORCH_CHECK(w_perm.size(1) == (long)R * S * IC + IC2,
-              "w_perm must be (OC, R*S*IC + IC2)");
-  const int path = airtc_conv2d_splitk_for(B, HO, WO, OC, IC);
-  TORCH_CHECK(path != 0 || (!x2p && !up),
-              "x2 / upsample2x need the MFMA path (IC % 32 == 0)");
-  TORCH_CHECK(!(x2p && up), "x2 and upsample2x exclude each other");
-  if (path == 0) {
-    airtc_conv2d_direct(h_ptr(x), h_ptr(w_perm), bp, cb, res, h_ptr_mut(out),
-                        B, H, W, IC, HO, WO, OC, (int)R, (int)S, (int)stride,
-                        (int)pad, (int)act, aff, (int)in_act, cur_stream());
-    return out;
-  }
-  float* wsp = nullptr;
-  torch::Tensor ws;
-  const int splitk = path > 0 ? path : -path;
-  if (splitk > 1) {
-    ws = torch::empty({(long)B * splitk, (long)HO * WO, OC},
-                      x.options().dtype(torch::kFloat));
-    wsp = ws.data_ptr<float>();
-  }
-  float* gnp = nullptr;
-  if (gn_part && stats_groups > 0 && aligned16(bp) && aligned16(cb) &&
-      aligned16(res)) {
-    const int npart = airtc_conv2d_stats_nchunk(B, HO, WO, OC, IC,
-                                                (int)stats_groups, (int)act);
-    if (npart > 0) {
-      *gn_part = torch::empty({(long)B * stats_groups, npart, 2},
-                              x.options().dtype(torch::kFloat));
-      gnp = gn_part->data_ptr<float>();
-    }
-  }
-  const int wrote = airtc_conv2d_mfma(
-      h_ptr(x), h_ptr(w_perm), bp, cb, res, h_ptr_mut(out), wsp, B, H, W, IC,
-      HO, WO, OC, (int)R, (int)S, (int)stride, (int)pad, (int)act, path, aff,
-      (int)in_act, gnp, (int)stats_groups, x2p, IC2, up, cur_stream());
-  // the launcher has the last word: partials it did not write are dropped,
-  // and the consumer norm runs its own statistics pass
-  if (gnp && !wrote) *gn_part = torch::Tensor();
-  return out;
+using OptTensor = c10::optional<torch::Tensor>;
+constexpr int64_t kIntMax = std::numeric_limits<int>::max();
+constexpr int64_t kGridYZ = 65535;  // largest gridDim.y / gridDim.z
+
+// an operand a kernel reads: on x's device, contiguous, of dtype dt
+void check_operand(const torch::Tensor& t, const torch::Tensor& x,
+                   c10::ScalarType dt, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.device() == x.device(), what,
+              " must be on the input's GPU");
+  TORCH_CHECK(t.is_contiguous(), what, " must be contiguous");
+  TORCH_CHECK(t.scalar_type() == dt, what, " must be ", dt, ", got ",
+              t.scalar_type());
 }
 
-torch::Tensor conv2d(torch::Tensor x, torch::Tensor w_perm,
-                     c10::optional<torch::Tensor> bias,
-                     c10::optional<torch::Tensor> cbias,
-                     c10::optional<torch::Tensor> residual, int64_t R,
-                     int64_t S, int64_t stride, int64_t pad, int64_t act,
-                     c10::optional<torch::Tensor> in_affine, int64_t in_act,
-                     c10::optional<torch::Tensor> x2, bool upsample2x) {
-  return conv2d_impl(x, w_perm, bias, cbias, residual, R, S, stride, pad, act,
-                     in_affine, in_act, 0, nullptr, x2, upsample2x);
+// the same operand with its element count
+void check_operand(const torch::Tensor& t, const torch::Tensor& x,
+                   c10::ScalarType dt, int64_t n, const char* what) {
+  check_operand(t, x, dt, what);
+  TORCH_CHECK(t.numel() == n, what, " must hold ", n, " values, got ",
+              t.numel());
+}
+
+// an optional one: its pointer, null when absent
+template <typename T>
+const T* opt_operand(const OptTensor& t, const torch::Tensor& x,
+                     c10::ScalarType dt, int64_t n, const char* what) {
+  if (!t.has_value()) return nullptr;
+  check_operand(*t, x, dt, n, what);
+  return static_cast<const T*>(t->data_ptr());
+}
+
+// --- conv (conv2d.hip, conv2d_fp8.hip) ---------------------------------
+// which launcher the problem is for: it decides the weight layout, the
+// input dtype and the operands that may come along
+enum ConvKind { CONV_F16, CONV_TINYIC, CONV_FP8 };
+
+struct ConvProblem {
+  AirtcConvArgs a = {};
+  torch::Tensor out, ws;  // own a.out and a.ws
+  bool empty = false;     // no output element: nothing to launch
+};
+
+// The one place a conv's tensors become a launcher record: derives the
+// extents, validates every operand, refuses sizes the kernels' index
+// arithmetic cannot hold, allocates the output and the split-K workspace.
+// want_q8 (fp8): u8 e4m3 output where the shape takes no split-K, since the
+// finalize pass stays fp8-agnostic; callers dispatch on the returned dtype.
+ConvProblem conv_problem(ConvKind kind, const torch::Tensor& x,
+                         const torch::Tensor& w, const OptTensor& bias,
+                         const OptTensor& cbias, const OptTensor& residual,
+                         int64_t R, int64_t S, int64_t stride, int64_t pad,
+                         int64_t act, const OptTensor& in_affine,
+                         int64_t in_act, const OptTensor& x2, bool upsample2x,
+                         bool want_q8) {
+  ConvProblem p;
+  AirtcConvArgs& a = p.a;
+  const bool x_q8 = kind == CONV_FP8 && x.scalar_type() == torch::kByte;
+  check_operand(x, x, x_q8 ? torch::kByte : torch::kHalf, "x");
+  check_operand(w, x,
+                kind == CONV_F16      ? torch::kHalf
+                : kind == CONV_TINYIC ? torch::kFloat
+                                      : torch::kByte,
+                "w");
+  TORCH_CHECK(x.dim() == 4 && w.dim() == 2,
+              "x must be (B, H, W, IC) and the weight 2-D");
+  TORCH_CHECK(R >= 1 && S >= 1 && stride >= 1 && pad >= 0, "conv needs R, S ",
+              ">= 1, stride >= 1, pad >= 0, got ", R, "x", S, " stride ",
+              stride, " pad ", pad);
+  const int up = upsample2x ? 1 : 0;
+  const int64_t B = x.size(0), IC = x.size(3);
+  const int64_t H = x.size(1) << up, W = x.size(2) << up;
+  const int64_t OC = kind == CONV_TINYIC ? w.size(1) : w.size(0);
+  // every extent is an int in the kernels, and so is a tap's coordinate
+  // hi = ho * stride + r - pad < H + 2 * pad: 2^29 each keeps both in range
+  TORCH_CHECK(std::max({B, H, W, IC, OC, R, S, stride, pad}) <= (1 << 29),
+              "conv extents must stay within 2^29");
+  TORCH_CHECK(IC >= 1, "conv needs input channels");
+  // (C++ division truncates towards zero, so test before dividing)
+  TORCH_CHECK(H + 2 * pad >= R && W + 2 * pad >= S, "kernel ", R, "x", S,
+              " is larger than the padded input ", H + 2 * pad, "x",
+              W + 2 * pad);
+  const int64_t HO = (H + 2 * pad - R) / stride + 1;
+  const int64_t WO = (W + 2 * pad - S) / stride + 1;
+  const int64_t M = HO * WO;
+  // M = HO * WO is an int in every kernel
+  TORCH_CHECK(M <= kIntMax, "HO * WO must fit 31 bits");
+
+  int64_t IC2 = 0;
+  if (x2.has_value()) {
+    check_operand(*x2, x, torch::kHalf, "x2");
+    TORCH_CHECK(x2->dim() == 4 && x2->size(0) == B && x2->size(1) == HO &&
+                    x2->size(2) == WO,
+                "x2 must be (B, HO, WO, IC2)");
+    IC2 = x2->size(3);
+    TORCH_CHECK(stride == 1 && IC2 > 0 && IC2 % 32 == 0,
+                "x2 needs stride 1 and IC2 % 32 == 0");
+    // the kernel offsets x2 per batch in 32 bits:
+    // (ho * WO + wo) * IC2 + k8 in load_tile
+    TORCH_CHECK(M * IC2 < (1L << 31), "x2 too large");
+    a.x2 = h_ptr(*x2);
+  }
+  TORCH_CHECK(!(a.x2 && up), "x2 and upsample2x exclude each other");
+  // K = R*S*IC + IC2 is an int, and the fp8 K loop forms kt * 128 + 64
+  // one tile past it
+  TORCH_CHECK(R * S <= kIntMax && R * S * IC + IC2 <= kIntMax - 192,
+              "R * S * IC + IC2 must fit 31 bits");
+  const int64_t K = R * S * IC + IC2;
+  if (kind == CONV_TINYIC) {
+    TORCH_CHECK(airtc_conv2d_tinyic_ok((int)IC, (int)R, (int)S),
+                "conv2d_tinyic needs IC <= 4 and R*S*IC <= 36");
+    TORCH_CHECK(w.size(0) == 36, "w_tiny must be (36, OC) f32");
+  } else {
+    TORCH_CHECK(w.size(1) == K, "the weight must be (OC, R*S*IC + IC2) = (",
+                OC, ", ", K, "), got (", w.size(0), ", ", w.size(1), ")");
+    TORCH_CHECK(kind != CONV_FP8 || IC % 64 == 0,
+                "fp8 conv path requires IC % 64 == 0");
+  }
+
+  // 0 = direct, +k = BM128 split-K k, -k = BM64 split-K k; the fp8 kernel
+  // has no direct form and picks a geometry by M
+  p.empty = B == 0 || OC == 0;
+  int path = 0;
+  if (!p.empty && kind != CONV_TINYIC) {
+    path = airtc_conv2d_splitk_for((int)B, (int)HO, (int)WO, (int)OC, (int)IC);
+    if (kind == CONV_FP8 && path == 0) path = M >= 2048 ? 1 : -1;
+  }
+  const int64_t splitk = path > 0 ? path : -path;
+  TORCH_CHECK(kind == CONV_F16 || (!a.x2 && !up),
+              "x2 / upsample2x belong to the f16 MFMA conv");
+  TORCH_CHECK(p.empty || path != 0 || (!a.x2 && !up),
+              "x2 / upsample2x need the MFMA path (IC % 32 == 0)");
+  const bool q8 = want_q8 && splitk == 1;
+  p.out = torch::empty({B, HO, WO, OC},
+                       x.options().dtype(q8 ? torch::kByte : torch::kHalf));
+
+  a.bias = opt_operand<float>(bias, x, torch::kFloat, OC, "bias");
+  a.cbias = opt_operand<uint16_t>(cbias, x, torch::kHalf, B * OC, "cbias");
+  a.residual = opt_operand<uint16_t>(residual, x, torch::kHalf, p.out.numel(),
+                                     "residual");
+  a.in_aff = opt_operand<float>(in_affine, x, torch::kFloat, B * IC * 2,
+                                "in_affine (B, IC, 2)");
+  TORCH_CHECK(!a.in_aff || (kind != CONV_TINYIC && !x_q8),
+              "the tiny-IC kernel and pre-quantized input take no fused "
+              "input affine");
+  if (p.empty) return p;
+
+  if (kind == CONV_TINYIC) {
+    // grid = (ceil(B*M / ppb), ceil(OC / 64)) with ppb >= 8
+    TORCH_CHECK((B * M + 7) / 8 <= kIntMax && OC <= kGridYZ * 64,
+                "conv2d_tinyic: too many pixels or channels for one grid");
+  } else if (path == 0) {
+    // small-IC kernel: grid.y = ceil(OC / 64); its grid.x and the direct
+    // kernel's grid are capped and stride in 64 bits
+    TORCH_CHECK(OC <= kGridYZ * 64, "conv2d: too many output channels");
+  } else {
+    // grid = (ceil(M / BM) * ceil(OC / 64), 1, B * splitk)
+    const int64_t bm = path > 0 ? 128 : 64;
+    TORCH_CHECK(B * splitk <= kGridYZ, "conv2d: batch ", B, " x split-K ",
+                splitk, " exceeds the grid's z extent");
+    TORCH_CHECK((M + bm - 1) / bm * ((OC + 63) / 64) <= kIntMax,
+                "conv2d: too many tiles for one grid");
+    // the vectorized finalize puts OC / (4 * ct) <= OC / 4 tiles in grid.y
+    TORCH_CHECK(splitk == 1 || OC <= kGridYZ * 4,
+                "conv2d: too many output channels for the split-K finalize");
+  }
+  if (splitk > 1) {
+    p.ws = torch::empty({B * splitk, M, OC}, x.options().dtype(torch::kFloat));
+    a.ws = p.ws.data_ptr<float>();
+  }
+  a.x = x.data_ptr();
+  a.w = w.data_ptr();
+  a.out = q8 ? nullptr : h_ptr_mut(p.out);
+  a.B = B, a.H = H, a.W = W, a.IC = IC, a.HO = HO, a.WO = WO, a.OC = OC;
+  a.R = R, a.S = S, a.stride = stride, a.pad = pad;
+  a.act = act, a.in_act = in_act, a.path = path, a.IC2 = IC2, a.up = up;
+  return p;
+}
+
+// f16 conv. stats_groups > 0 asks the split-K finalize for GroupNorm
+// partials of the output (kernels.h layout) for a consumer norm with that
+// many groups: (out, partials), or (out, None) when the shape takes no
+// finalize pass or the finalize cannot produce them.
+// x2: optional second K segment (B, HO, WO, IC2), w_perm then (OC, R*S*IC +
+// IC2); upsample2x: x is read through nearest-2x addressing (MFMA path only)
+pybind11::tuple conv2d(torch::Tensor x, torch::Tensor w_perm, OptTensor bias,
+                       OptTensor cbias, OptTensor residual, int64_t R,
+                       int64_t S, int64_t stride, int64_t pad, int64_t act,
+                       OptTensor in_affine, int64_t in_act,
+                       int64_t stats_groups, OptTensor x2, bool upsample2x) {
+  TORCH_CHECK(stats_groups >= 0 && stats_groups <= kIntMax,
+              "stats_groups out of range");
+  auto p = conv_problem(CONV_F16, x, w_perm, bias, cbias, residual, R, S,
+                        stride, pad, act, in_affine, in_act, x2, upsample2x,
+                        false);
+  AirtcConvArgs& a = p.a;
+  torch::Tensor part;
+  if (p.empty) return pybind11::make_tuple(p.out, pybind11::none());
+  if (a.path == 0) {
+    airtc_conv2d_direct(&a, cur_stream());
+  } else {
+    a.gn_groups = (int)stats_groups;
+    if (stats_groups > 0 && aligned16(a.bias) && aligned16(a.cbias) &&
+        aligned16(a.residual)) {
+      const int npart = airtc_conv2d_stats_nchunk(a.B, a.HO, a.WO, a.OC, a.IC,
+                                                  a.gn_groups, a.act);
+      if (npart > 0) {
+        part = torch::empty({a.B * stats_groups, npart, 2},
+                            x.options().dtype(torch::kFloat));
+        a.gn_part = part.data_ptr<float>();
+      }
+    }
+    // the launcher has the last word: partials it did not write are dropped,
+    // and the consumer norm runs its own statistics pass
+    if (!airtc_conv2d_mfma(&a, cur_stream())) part = torch::Tensor();
+  }
+  if (part.defined()) return pybind11::make_tuple(p.out, part);
+  return pybind11::make_tuple(p.out, pybind11::none());
 }
 
 // tiny-IC conv (IC <= 4, K <= 36): lanes along OC (conv2d.hip). w_tiny is the
 // (36, OC) f32 pack of the weight.
 torch::Tensor conv2d_tinyic(torch::Tensor x, torch::Tensor w_tiny,
-                            c10::optional<torch::Tensor> bias,
-                            c10::optional<torch::Tensor> cbias,
-                            c10::optional<torch::Tensor> residual, int64_t R,
-                            int64_t S, int64_t stride, int64_t pad,
-                            int64_t act) {
-  CHECK_IN(x);
-  CHECK_IN(w_tiny);
-  TORCH_CHECK(x.dtype() == torch::kHalf && x.dim() == 4);
-  const int B = x.size(0), H = x.size(1), W = x.size(2), IC = x.size(3);
-  TORCH_CHECK(airtc_conv2d_tinyic_ok(IC, (int)R, (int)S),
-              "conv2d_tinyic needs IC <= 4 and R*S*IC <= 36");
-  TORCH_CHECK(w_tiny.dtype() == torch::kFloat && w_tiny.dim() == 2 &&
-                  w_tiny.size(0) == 36,
-              "w_tiny must be (36, OC) f32");
-  TORCH_CHECK(stride >= 1 && pad >= 0);
-  const int OC = w_tiny.size(1);
-  const int HO = (H + 2 * (int)pad - (int)R) / (int)stride + 1;
-  const int WO = (W + 2 * (int)pad - (int)S) / (int)stride + 1;
-  TORCH_CHECK(HO > 0 && WO > 0);
-  auto out = torch::empty({B, HO, WO, OC}, x.options());
-  const float* bp = nullptr;
-  if (bias.has_value()) {
-    CHECK_IN((*bias));
-    TORCH_CHECK(bias->dtype() == torch::kFloat && bias->numel() == OC);
-    bp = bias->data_ptr<float>();
-  }
-  const uint16_t* cb = nullptr;
-  if (cbias.has_value()) {
-    CHECK_IN((*cbias));
-    TORCH_CHECK(cbias->dtype() == torch::kHalf &&
-                cbias->numel() == (long)B * OC);
-    cb = h_ptr(*cbias);
-  }
-  const uint16_t* res = nullptr;
-  if (residual.has_value()) {
-    CHECK_IN((*residual));
-    TORCH_CHECK(residual->dtype() == torch::kHalf);
-    TORCH_CHECK(residual->numel() == out.numel(), "residual shape mismatch");
-    res = h_ptr(*residual);
-  }
-  if (out.numel() == 0) return out;
-  airtc_conv2d_tinyic(h_ptr(x), w_tiny.data_ptr<float>(), bp, cb, res,
-                      h_ptr_mut(out), B, H, W, IC, HO, WO, OC, (int)R, (int)S,
-                      (int)stride, (int)pad, (int)act, cur_stream());
-  return out;
+                            OptTensor bias, OptTensor cbias,
+                            OptTensor residual, int64_t R, int64_t S,
+                            int64_t stride, int64_t pad, int64_t act) {
+  auto p = conv_problem(CONV_TINYIC, x, w_tiny, bias, cbias, residual, R, S,
+                        stride, pad, act, c10::nullopt, 0, c10::nullopt, false,
+                        false);
+  if (!p.empty) airtc_conv2d_tinyic(&p.a, cur_stream());
+  return p.out;
 }
 
-// conv2d + GroupNorm partials for the consumer norm: (out, partials | None)
-pybind11::tuple conv2d_stats(torch::Tensor x, torch::Tensor w_perm,
-                             c10::optional<torch::Tensor> bias,
-                             c10::optional<torch::Tensor> cbias,
-                             c10::optional<torch::Tensor> residual, int64_t R,
-                             int64_t S, int64_t stride, int64_t pad,
-                             int64_t act,
-                             c10::optional<torch::Tensor> in_affine,
-                             int64_t in_act, int64_t stats_groups,
-                             c10::optional<torch::Tensor> x2,
-                             bool upsample2x) {
-  torch::Tensor part;
-  auto out = conv2d_impl(x, w_perm, bias, cbias, residual, R, S, stride, pad,
-                         act, in_affine, in_act, stats_groups, &part, x2,
-                         upsample2x);
-  if (part.defined()) return pybind11::make_tuple(out, part);
-  return pybind11::make_tuple(out, pybind11::none());
+// fp8 conv: MX-scaled MFMA path (conv2d_fp8.hip). Same surface as conv2d
+// but weights are pre-quantized e4m3 bytes + per-OC dequant scales, and the
+// activation scale rides along as a scalar. out_scale > 0 asks for e4m3
+// output (conv_problem, want_q8).
+torch::Tensor conv2d_fp8(torch::Tensor x, torch::Tensor w_fp8,
+                         torch::Tensor dq, double a_scale, OptTensor bias,
+                         OptTensor cbias, OptTensor residual, int64_t R,
+                         int64_t S, int64_t stride, int64_t pad, int64_t act,
+                         OptTensor in_affine, int64_t in_act,
+                         double out_scale) {
+  auto p = conv_problem(CONV_FP8, x, w_fp8, bias, cbias, residual, R, S,
+                        stride, pad, act, in_affine, in_act, c10::nullopt,
+                        false, out_scale > 0);
+  check_operand(dq, x, torch::kFloat, w_fp8.size(0), "dq (f32[OC])");
+  if (p.empty) return p.out;
+  const bool q8 = p.out.scalar_type() == torch::kByte;
+  airtc_conv2d_fp8_mfma(&p.a, dq.data_ptr<float>(), (float)a_scale,
+                        x.scalar_type() == torch::kByte ? 1 : 0,
+                        q8 ? p.out.data_ptr<uint8_t>() : nullptr,
+                        q8 ? (float)(1.0 / out_scale) : 0.f, cur_stream());
+  return p.out;
+}
+
+// --- GroupNorm (norms.hip) ---------------------------------------------
+// the operands every GroupNorm binding shares; x is (B, ..., C)
+struct GnShape {
+  int B, HW, C;
+};
+
+GnShape check_group_norm(const torch::Tensor& x, int64_t groups,
+                         const torch::Tensor& gamma,
+                         const torch::Tensor& beta) {
+  check_operand(x, x, torch::kHalf, "x");
+  TORCH_CHECK(x.dim() >= 2, "group_norm: x must be (B, ..., C)");
+  const int64_t B = x.size(0), C = x.size(-1);
+  // the kernels read channel pairs that must not straddle a group
+  TORCH_CHECK(groups >= 1 && C % groups == 0 && (C / groups) % 2 == 0,
+              "group_norm: groups must divide C into an even number of "
+              "channels each, got C=", C, " groups=", groups);
+  check_operand(gamma, x, torch::kFloat, C, "gamma");
+  check_operand(beta, x, torch::kFloat, C, "beta");
+  const int64_t HW = B * C > 0 ? x.numel() / (B * C) : 0;
+  // grid.x = B * G blocks (airtc_group_norm_nchunk forms B * G in an int as
+  // well), and HW and C are ints in the kernels; the workspace of
+  // B * G * AIRTC_GN_MAX_PART pairs is then addressed in 64 bits
+  TORCH_CHECK(B * groups <= kIntMax && HW <= kIntMax && C <= kIntMax,
+              "group_norm: B*G, HW and C must fit 31 bits");
+  return {(int)B, (int)HW, (int)C};
+}
+
+torch::Tensor gn_workspace(const torch::Tensor& x, int B, int64_t groups) {
+  return torch::empty({B * groups * AIRTC_GN_MAX_PART * 2},
+                      x.options().dtype(torch::kFloat));
 }
 
 torch::Tensor group_norm_coeffs(torch::Tensor x, int64_t groups,
                                 torch::Tensor gamma, torch::Tensor beta,
                                 double eps) {
-  CHECK_IN(x);
-  const int B = x.size(0);
-  const int C = x.size(-1);
-  const long HW = x.numel() / ((long)B * C);
-  auto coeffs = torch::empty({B, C, 2}, x.options().dtype(torch::kFloat));
-  auto ws = torch::empty({(long)B * groups * AIRTC_GN_MAX_PART * 2},
-                         x.options().dtype(torch::kFloat));
+  const GnShape d = check_group_norm(x, groups, gamma, beta);
+  auto coeffs = torch::empty({d.B, d.C, 2}, x.options().dtype(torch::kFloat));
+  if (coeffs.numel() == 0) return coeffs;
+  auto ws = gn_workspace(x, d.B, groups);
   airtc_group_norm_coeffs(h_ptr(x), gamma.data_ptr<float>(),
                           beta.data_ptr<float>(), coeffs.data_ptr<float>(),
-                          ws.data_ptr<float>(), B, (int)HW, C, (int)groups,
+                          ws.data_ptr<float>(), d.B, d.HW, d.C, (int)groups,
                           (float)eps, cur_stream());
   return coeffs;
 }
@@ -249,27 +350,23 @@ torch::Tensor group_norm_into(const torch::Tensor& x, torch::Tensor out,
                               const torch::Tensor& beta, double eps,
                               int64_t act, double a_scale,
                               const c10::optional<torch::Tensor>& partials) {
-  CHECK_IN(x);
-  TORCH_CHECK(x.dtype() == torch::kHalf);
-  const int B = x.size(0);
-  const int C = x.size(-1);
-  const long HW = x.numel() / ((long)B * C);
+  const GnShape d = check_group_norm(x, groups, gamma, beta);
+  if (x.numel() == 0) return out;
   const bool q8 = out.dtype() == torch::kUInt8;
   const float* part = nullptr;
   int npart = 0;
   torch::Tensor ws;
   float* wsp = nullptr;
   if (partials.has_value()) {
-    npart = check_partials(*partials, B, groups);
+    npart = check_partials(*partials, d.B, groups);
     part = partials->data_ptr<float>();
   } else {
-    ws = torch::empty({(long)B * groups * AIRTC_GN_MAX_PART * 2},
-                      x.options().dtype(torch::kFloat));
+    ws = gn_workspace(x, d.B, groups);
     wsp = ws.data_ptr<float>();
   }
   airtc_group_norm(h_ptr(x), part, npart, gamma.data_ptr<float>(),
                    beta.data_ptr<float>(), q8 ? nullptr : h_ptr_mut(out),
-                   q8 ? out.data_ptr<uint8_t>() : nullptr, wsp, B, (int)HW, C,
+                   q8 ? out.data_ptr<uint8_t>() : nullptr, wsp, d.B, d.HW, d.C,
                    (int)groups, (float)eps, (int)act, (float)a_scale,
                    cur_stream());
   return out;
@@ -344,7 +441,11 @@ torch::Tensor attention_bhlc(torch::Tensor q, torch::Tensor k, torch::Tensor v,
 
 torch::Tensor silu(torch::Tensor x) {
   CHECK_IN(x);
+  TORCH_CHECK(x.dtype() == torch::kHalf, "silu: x must be float16");
+  TORCH_CHECK(x.numel() % 8 == 0, "silu: the kernel handles 8 elements per "
+              "lane, numel must be a multiple of 8, got ", x.numel());
   auto out = torch::empty_like(x);
+  if (x.numel() == 0) return out;
   airtc_silu_f16(h_ptr(x), h_ptr_mut(out), x.numel(), cur_stream());
   return out;
 }
@@ -381,17 +482,28 @@ torch::Tensor add_act(torch::Tensor a, torch::Tensor b, int64_t act) {
 
 torch::Tensor upsample2x(torch::Tensor x) {
   CHECK_IN(x);
+  TORCH_CHECK(x.dtype() == torch::kHalf, "upsample2x: x must be float16");
+  TORCH_CHECK(x.dim() == 4, "upsample2x: x must be (B, H, W, C)");
+  TORCH_CHECK(x.size(3) % 8 == 0, "upsample2x: the kernel copies 8 channels "
+              "per lane, C must be a multiple of 8, got ", x.size(3));
+  // B, 2 * H, 2 * W and C / 8 are ints in the kernel
+  TORCH_CHECK(std::max({x.size(0), x.size(1), x.size(2), x.size(3)}) <=
+                  kIntMax / 2,
+              "upsample2x: extents must fit 30 bits");
   const int B = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
   auto out = torch::empty({B, 2 * H, 2 * W, C}, x.options());
+  if (out.numel() == 0) return out;
   airtc_upsample2x_f16(h_ptr(x), h_ptr_mut(out), B, H, W, C, cur_stream());
   return out;
 }
 
 torch::Tensor preprocess_u8(torch::Tensor frame) {
   CHECK_IN(frame);
-  TORCH_CHECK(frame.dtype() == torch::kUInt8);
+  TORCH_CHECK(frame.dtype() == torch::kUInt8,
+              "preprocess_u8: frame must be uint8");  // any element count
   auto out = torch::empty(frame.sizes(),
                           frame.options().dtype(torch::kHalf));
+  if (frame.numel() == 0) return out;
   airtc_preprocess_u8(frame.data_ptr<uint8_t>(),
                       reinterpret_cast<uint16_t*>(out.data_ptr<at::Half>()),
                       frame.numel(), cur_stream());
@@ -400,8 +512,10 @@ torch::Tensor preprocess_u8(torch::Tensor frame) {
 
 torch::Tensor postprocess_u8(torch::Tensor img) {
   CHECK_IN(img);
-  TORCH_CHECK(img.dtype() == torch::kHalf);
+  TORCH_CHECK(img.dtype() == torch::kHalf,
+              "postprocess_u8: img must be float16");  // any element count
   auto out = torch::empty(img.sizes(), img.options().dtype(torch::kUInt8));
+  if (img.numel() == 0) return out;
   airtc_postprocess_u8(h_ptr(img), out.data_ptr<uint8_t>(), img.numel(),
                        cur_stream());
   return out;
@@ -743,19 +857,36 @@ pybind11::dict vcn_probe() {
 }
 
 // fused LCM scheduler math (elementwise.hip): one kernel per scheduler op
+// the two tensors of a scheduler op, (B, ...) f16 with rows of a multiple of
+// 8 elements (one 16-byte access per lane); returns the row size, 0 when
+// there is nothing to compute
+long sched_rows(const torch::Tensor& x, const torch::Tensor& y,
+                const char* op) {
+  TORCH_CHECK(x.dim() >= 1, op, ": tensors must be (B, ...)");
+  check_operand(x, x, torch::kHalf, op);
+  check_operand(y, x, torch::kHalf, x.numel(), op);
+  if (x.numel() == 0) return 0;
+  const long per_b = x.numel() / x.size(0);
+  TORCH_CHECK(per_b % 8 == 0, op, ": row size must be a multiple of 8, got ",
+              per_b);
+  return per_b;
+}
+
+// a per-batch-row coefficient array: (B,) f32 on x's device
+const float* sched_coef(const torch::Tensor& c, const torch::Tensor& x,
+                        const char* what) {
+  check_operand(c, x, torch::kFloat, x.size(0), what);
+  return c.data_ptr<float>();
+}
+
 torch::Tensor sched_add_noise(torch::Tensor x0, torch::Tensor noise,
                               torch::Tensor a, torch::Tensor bt) {
-  CHECK_IN(x0);
-  CHECK_IN(noise);
-  TORCH_CHECK(x0.dtype() == torch::kHalf && noise.dtype() == torch::kHalf);
-  TORCH_CHECK(a.dtype() == torch::kFloat && bt.dtype() == torch::kFloat);
-  const long B = x0.size(0);
-  TORCH_CHECK(a.numel() == B && bt.numel() == B, "coeffs must be (B,)");
-  const long per_b = x0.numel() / B;
-  TORCH_CHECK(per_b % 8 == 0, "row size must be a multiple of 8");
+  const long per_b = sched_rows(x0, noise, "sched_add_noise");
+  const float* ap = sched_coef(a, x0, "a");
+  const float* bp = sched_coef(bt, x0, "bt");
   auto out = torch::empty_like(x0);
-  airtc_sched_add_noise(h_ptr(x0), h_ptr(noise), a.data_ptr<float>(),
-                        bt.data_ptr<float>(), h_ptr_mut(out), per_b,
+  if (per_b == 0) return out;
+  airtc_sched_add_noise(h_ptr(x0), h_ptr(noise), ap, bp, h_ptr_mut(out), per_b,
                         x0.numel(), cur_stream());
   return out;
 }
@@ -763,15 +894,13 @@ torch::Tensor sched_add_noise(torch::Tensor x0, torch::Tensor noise,
 torch::Tensor sched_blend(torch::Tensor xt, torch::Tensor eps,
                           torch::Tensor a, torch::Tensor bt,
                           torch::Tensor c_out, torch::Tensor c_skip) {
-  CHECK_IN(xt);
-  CHECK_IN(eps);
-  TORCH_CHECK(xt.dtype() == torch::kHalf && eps.dtype() == torch::kHalf);
-  const long B = xt.size(0);
-  TORCH_CHECK(a.numel() == B && bt.numel() == B && c_out.numel() == B &&
-              c_skip.numel() == B, "coeffs must be (B,)");
-  const long per_b = xt.numel() / B;
-  TORCH_CHECK(per_b % 8 == 0, "row size must be a multiple of 8");
+  const long per_b = sched_rows(xt, eps, "sched_blend");
+  sched_coef(a, xt, "a");
+  sched_coef(bt, xt, "bt");
+  sched_coef(c_out, xt, "c_out");
+  sched_coef(c_skip, xt, "c_skip");
   auto out = torch::empty_like(xt);
+  if (per_b == 0) return out;
   airtc_sched_blend(h_ptr(xt), h_ptr(eps), a.data_ptr<float>(),
                     bt.data_ptr<float>(), c_out.data_ptr<float>(),
                     c_skip.data_ptr<float>(), h_ptr_mut(out), per_b,
@@ -831,95 +960,6 @@ torch::Tensor rcfg_apply(int64_t mode, torch::Tensor eps, torch::Tensor coef,
   return out;
 }
 
-// fp8 conv: MX-scaled MFMA path (conv2d_fp8.hip). Same surface as conv2d
-// but weights are pre-quantized e4m3 bytes + per-OC dequant scales, and the
-// activation scale rides along as a scalar.
-torch::Tensor conv2d_fp8(torch::Tensor x, torch::Tensor w_fp8,
-                         torch::Tensor dq, double a_scale,
-                         c10::optional<torch::Tensor> bias,
-                         c10::optional<torch::Tensor> cbias,
-                         c10::optional<torch::Tensor> residual, int64_t R,
-                         int64_t S, int64_t stride, int64_t pad, int64_t act,
-                         c10::optional<torch::Tensor> in_affine,
-                         int64_t in_act, double out_scale) {
-  CHECK_IN(x);
-  CHECK_IN(w_fp8);
-  CHECK_IN(dq);
-  const bool x_q8 = x.dtype() == torch::kUInt8;
-  TORCH_CHECK(x_q8 || x.dtype() == torch::kHalf,
-              "x must be f16 or u8 e4m3 codes");
-  TORCH_CHECK(w_fp8.dtype() == torch::kUInt8, "w_fp8 must be e4m3 bytes");
-  TORCH_CHECK(dq.dtype() == torch::kFloat, "dq must be f32[OC]");
-  const int B = x.size(0), H = x.size(1), W = x.size(2), IC = x.size(3);
-  const int OC = w_fp8.size(0);
-  TORCH_CHECK(IC % 64 == 0, "fp8 conv path requires IC % 64 == 0");
-  TORCH_CHECK(dq.numel() == OC, "dq must have OC entries");
-  TORCH_CHECK(w_fp8.size(1) == (long)R * S * IC, "w_fp8 must be (OC, R*S*IC)");
-  TORCH_CHECK(!(x_q8 && in_affine.has_value()),
-              "pre-quantized input cannot take a fused input affine");
-  const int HO = (H + 2 * (int)pad - (int)R) / (int)stride + 1;
-  const int WO = (W + 2 * (int)pad - (int)S) / (int)stride + 1;
-  int path0 = airtc_conv2d_splitk_for(B, HO, WO, OC, IC);
-  if (path0 == 0) path0 = HO * WO >= 2048 ? 1 : -1;
-  const int splitk0 = path0 > 0 ? path0 : -path0;
-  // q8 output only on the split-K-free path (the finalize pass stays
-  // fp8-agnostic); callers get f16 back otherwise and must dispatch on
-  // the returned dtype
-  const bool want_q8 = out_scale > 0 && splitk0 == 1;
-  auto out = torch::empty({B, HO, WO, OC},
-                          x.options().dtype(want_q8 ? torch::kUInt8
-                                                    : torch::kHalf));
-  const float* bp = nullptr;
-  if (bias.has_value()) {
-    TORCH_CHECK(bias->dtype() == torch::kFloat && bias->is_contiguous());
-    bp = bias->data_ptr<float>();
-  }
-  const uint16_t* cb = nullptr;
-  if (cbias.has_value()) {
-    CHECK_IN((*cbias));
-    TORCH_CHECK(cbias->dtype() == torch::kHalf);
-    cb = h_ptr(*cbias);
-  }
-  const uint16_t* res = nullptr;
-  if (residual.has_value()) {
-    CHECK_IN((*residual));
-    TORCH_CHECK(residual->dtype() == torch::kHalf);
-    TORCH_CHECK(residual->numel() == out.numel(), "residual shape mismatch");
-    res = h_ptr(*residual);
-  }
-  const float* aff = nullptr;
-  if (in_affine.has_value()) {
-    CHECK_IN((*in_affine));
-    TORCH_CHECK(in_affine->dtype() == torch::kFloat &&
-                    in_affine->numel() == (long)B * IC * 2,
-                "in_affine must be (B, IC, 2) f32");
-    aff = in_affine->data_ptr<float>();
-  }
-  const int path = path0;
-  const int splitk = splitk0;
-  float* wsp = nullptr;
-  torch::Tensor ws;
-  if (splitk > 1) {
-    ws = torch::empty({(long)B * splitk, (long)HO * WO, OC},
-                      x.options().dtype(torch::kFloat));
-    wsp = ws.data_ptr<float>();
-  }
-  const uint16_t* xp = x_q8
-                           ? reinterpret_cast<const uint16_t*>(
-                                 x.data_ptr<uint8_t>())
-                           : h_ptr(x);
-  uint16_t* op = want_q8 ? nullptr : h_ptr_mut(out);
-  uint8_t* oq = want_q8 ? out.data_ptr<uint8_t>() : nullptr;
-  airtc_conv2d_fp8_mfma(xp, w_fp8.data_ptr<uint8_t>(),
-                        dq.data_ptr<float>(), bp, cb, res, op, wsp,
-                        B, H, W, IC, HO, WO, OC, (int)R, (int)S, (int)stride,
-                        (int)pad, (int)act, path, aff, (int)in_act,
-                        (float)a_scale, x_q8 ? 1 : 0, oq,
-                        want_q8 ? (float)(1.0 / out_scale) : 0.f,
-                        cur_stream());
-  return out;
-}
-
 // fp8 hardware probes (fp8.hip): raw MX MFMA tile + fused scale-converts
 torch::Tensor fp8_mx_probe(torch::Tensor A, torch::Tensor B, int64_t sa,
                            int64_t sb) {
@@ -976,29 +1016,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("residual"));
   // how the error for a shape the library has no algorithm for begins
   m.attr("LT_NO_ALGORITHM") = "linear_residual: no hipBLASLt algorithm";
-  m.def("conv2d", &conv2d, "implicit-GEMM MFMA conv2d (NHWC)",
-        pybind11::arg("x"), pybind11::arg("w_perm"), pybind11::arg("bias"),
-        pybind11::arg("cbias"), pybind11::arg("residual"), pybind11::arg("R"),
-        pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"),
-        pybind11::arg("act"), pybind11::arg("in_affine") = pybind11::none(),
-        pybind11::arg("in_act") = 0, pybind11::arg("x2") = pybind11::none(),
+  m.def("conv2d", &conv2d,
+        "implicit-GEMM MFMA conv2d (NHWC): (out, partials | None); "
+        "stats_groups > 0 also asks for GroupNorm partials of the output for "
+        "a consumer norm with that many groups",
+        pybind11::arg("x"), pybind11::arg("w_perm"),
+        pybind11::arg("bias") = pybind11::none(),
+        pybind11::arg("cbias") = pybind11::none(),
+        pybind11::arg("residual") = pybind11::none(), pybind11::arg("R"),
+        pybind11::arg("S"), pybind11::arg("stride") = 1,
+        pybind11::arg("pad") = 0, pybind11::arg("act") = 0,
+        pybind11::arg("in_affine") = pybind11::none(),
+        pybind11::arg("in_act") = 0, pybind11::arg("stats_groups") = 0,
+        pybind11::arg("x2") = pybind11::none(),
         pybind11::arg("upsample2x") = false);
   m.def("conv2d_tinyic", &conv2d_tinyic,
         "tiny-IC conv (IC <= 4, K <= 36), lanes along OC (NHWC)",
-        pybind11::arg("x"), pybind11::arg("w_tiny"), pybind11::arg("bias"),
-        pybind11::arg("cbias"), pybind11::arg("residual"), pybind11::arg("R"),
-        pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"),
-        pybind11::arg("act"));
-  m.def("conv2d_stats", &conv2d_stats,
-        "conv2d that also returns GroupNorm partials of its output for a "
-        "consumer norm with stats_groups groups: (out, partials | None)",
-        pybind11::arg("x"), pybind11::arg("w_perm"), pybind11::arg("bias"),
-        pybind11::arg("cbias"), pybind11::arg("residual"), pybind11::arg("R"),
-        pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"),
-        pybind11::arg("act"), pybind11::arg("in_affine"),
-        pybind11::arg("in_act"), pybind11::arg("stats_groups"),
-        pybind11::arg("x2") = pybind11::none(),
-        pybind11::arg("upsample2x") = false);
+        pybind11::arg("x"), pybind11::arg("w_tiny"),
+        pybind11::arg("bias") = pybind11::none(),
+        pybind11::arg("cbias") = pybind11::none(),
+        pybind11::arg("residual") = pybind11::none(), pybind11::arg("R"),
+        pybind11::arg("S"), pybind11::arg("stride") = 1,
+        pybind11::arg("pad") = 0, pybind11::arg("act") = 0);
   m.def("group_norm_silu", &group_norm_silu, pybind11::arg("x"),
         pybind11::arg("groups"), pybind11::arg("gamma"), pybind11::arg("beta"),
         pybind11::arg("eps"), pybind11::arg("act"),
@@ -1046,10 +1085,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_fp8", &conv2d_fp8,
         "fp8 e4m3 implicit-GEMM conv2d on the MX-scaled MFMA (NHWC)",
         pybind11::arg("x"), pybind11::arg("w_fp8"), pybind11::arg("dq"),
-        pybind11::arg("a_scale"), pybind11::arg("bias"),
-        pybind11::arg("cbias"), pybind11::arg("residual"), pybind11::arg("R"),
-        pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"),
-        pybind11::arg("act"), pybind11::arg("in_affine") = pybind11::none(),
+        pybind11::arg("a_scale"), pybind11::arg("bias") = pybind11::none(),
+        pybind11::arg("cbias") = pybind11::none(),
+        pybind11::arg("residual") = pybind11::none(), pybind11::arg("R"),
+        pybind11::arg("S"), pybind11::arg("stride") = 1,
+        pybind11::arg("pad") = 0, pybind11::arg("act") = 0,
+        pybind11::arg("in_affine") = pybind11::none(),
         pybind11::arg("in_act") = 0, pybind11::arg("out_scale") = 0.0);
   m.def("fp8_mx_probe", &fp8_mx_probe,
         "raw-fragment v_mfma_scale_f32_16x16x128_f8f6f4 tile (layout probe)");

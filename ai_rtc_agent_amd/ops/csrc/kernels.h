@@ -101,74 +101,77 @@ void airtc_group_norm_coeffs(const uint16_t* x, const float* gamma,
                              hipStream_t s);
 
 // conv ----------------------------------------------------------------------
-// x   : (B, H, W, IC) NHWC f16 (zero-padding handled inline)
-// w   : (OC, R*S*IC) f16, k order = (r, s, ic)
-// cbias: optional per-(batch, out-channel) f16 bias (B, OC) — time-emb add
-// residual: optional f16 tensor with out's shape, added pre-activation
-// out : (B, HO, WO, OC) f16
-// path: from airtc_conv2d_splitk_for (0 = direct, +k = BM128 split-K k,
-//       -k = BM64 split-K k);
-// ws  : f32 workspace (B*k, HO*WO, OC) required when k > 1
+// One conv problem: the record every conv launcher takes. The host (ext.cpp,
+// conv_problem) fills and validates it; the launchers trust it.
+typedef struct AirtcConvArgs {
+  // (B, H >> up, W >> up, IC) NHWC f16, zero padding handled inline; the fp8
+  // launcher with x_is_q8 reads u8 e4m3 codes here instead
+  const void* x;
+  // the weight in the launcher's own layout: mfma / direct (OC, R*S*IC + IC2)
+  // f16, k order (r, s, ic) then the x2 segment; tinyic the (36, OC) f32 pack
+  // (row k = GEMM column k, rows past R*S*IC zero); fp8 (OC, R*S*IC) OCP e4m3
+  // bytes, quantized per OC on the host
+  const void* w;
+  const float* bias;         // optional (OC,) f32
+  const uint16_t* cbias;     // optional (B, OC) f16 per-(batch, out-channel)
+                             // bias: the time-embedding add
+  const uint16_t* residual;  // optional f16 of out's shape, added before act
+  uint16_t* out;             // (B, HO, WO, OC) f16
+  float* ws;                 // f32 split-K workspace (B*k, HO*WO, OC),
+                             // required when path is +-k with k > 1
+  // optional (B, IC, 2) f32 per-channel input affine (fused GroupNorm) with
+  // in_act applied after: transforms x AT LOAD TIME, padding stays zero.
+  // Applies to x only, never to x2. mfma, direct and fp8 (f16 x).
+  const float* in_aff;
+  // optional second K segment (mfma only): a (B, HO, WO, IC2) f16 tensor read
+  // as a 1x1 stride-1 tap at the output pixel, a resnet's pointwise shortcut.
+  // Needs stride == 1 and IC2 % 32 == 0; excludes up.
+  const uint16_t* x2;
+  // optional GroupNorm partials of the OUTPUT for a consumer norm with
+  // gn_groups groups (layout above), written by the split-K finalize from
+  // the rounded f16 values (mfma only). Pass it only when
+  // airtc_conv2d_stats_nchunk returns npart > 0 (split-K path, act ==
+  // ACT_NONE, OC % 4 == 0, even OC/G, B <= 65535); B*G*npart*2 floats; bias /
+  // cbias / residual 16 B aligned.
+  float* gn_part;
+  int B, H, W, IC;  // H, W: the extents the conv sees (upsampled when up)
+  int HO, WO, OC;
+  int R, S, stride, pad;
+  int act;      // epilogue: out = act(conv + bias + cbias + residual)
+  int in_act;   // with in_aff
+  int path;     // airtc_conv2d_splitk_for: 0 = direct, +k = BM128 split-K k,
+                // -k = BM64 split-K k (mfma, fp8: nonzero)
+  int IC2;      // channels of x2, 0 without
+  int up;       // 1 = x is read through nearest-2x addressing (mfma only)
+  int gn_groups;  // with gn_part
+} AirtcConvArgs;
+
 int airtc_conv2d_splitk_for(int B, int HO, int WO, int OC, int IC);
-// in_aff: optional (B, IC, 2) f32 per-channel input affine (fused GN) with
-// in_act applied after — transforms x AT LOAD TIME (padding stays zero)
-// Returns 1 when gn_part was written, 0 otherwise (the caller must then drop
-// the buffer: nothing initialised it).
-int airtc_conv2d_mfma(const uint16_t* x, const uint16_t* w, const float* bias,
-                      const uint16_t* cbias, const uint16_t* residual,
-                      uint16_t* out, float* ws, int B, int H, int W, int IC,
-                      int HO, int WO, int OC, int R, int S, int stride,
-                      int pad, int act, int path, const float* in_aff,
-                      int in_act, float* gn_part, int gn_groups,
-                      const uint16_t* x2, int IC2, int up, hipStream_t s);
-// x2/IC2: optional second K segment (pointwise tail): a (B, HO, WO, IC2)
-// tensor read as a 1x1 stride-1 tap at the output pixel; w rows are then
-// R*S*IC + IC2 long. Needs stride == 1 and IC2 % 32 == 0.
-// up: 1 = x is (B, H/2, W/2, IC) and is read through nearest-2x addressing;
-// H, W stay the extents the conv sees. x2 and up exclude each other (one
-// addressing mode per launch; returns -1 and launches nothing).
-// Tiny-IC conv (IC <= 4, R*S*IC <= 36; airtc_conv2d_tinyic_ok): lanes along
-// OC, wt is the (36, OC) f32 weight pack (row k = GEMM column k, rest zero).
-int airtc_conv2d_tinyic_ok(int IC, int R, int S);
-void airtc_conv2d_tinyic(const uint16_t* x, const float* wt, const float* bias,
-                         const uint16_t* cbias, const uint16_t* residual,
-                         uint16_t* out, int B, int H, int W, int IC, int HO,
-                         int WO, int OC, int R, int S, int stride, int pad,
-                         int act, hipStream_t s);
-// gn_part: optional GroupNorm partials of the OUTPUT for a consumer norm
-// with gn_groups groups (layout above), written by the split-K finalize from
-// the rounded f16 values. Pass it only when airtc_conv2d_stats_nchunk
-// returns npart > 0 (split-K path, act == ACT_NONE, OC % 4 == 0, even
-// OC/G, B <= 65535); size B*G*npart*2 floats; bias / cbias / residual 16 B
-// aligned.
+// partials the split-K finalize would write for this shape (see gn_part), 0
+// when it cannot produce them
 int airtc_conv2d_stats_nchunk(int B, int HO, int WO, int OC, int IC, int G,
                               int act);
-void airtc_conv2d_direct(const uint16_t* x, const uint16_t* w,
-                         const float* bias, const uint16_t* cbias,
-                         const uint16_t* residual, uint16_t* out, int B, int H,
-                         int W, int IC, int HO, int WO, int OC, int R, int S,
-                         int stride, int pad, int act, const float* in_aff,
-                         int in_act, hipStream_t s);
+// implicit-GEMM MFMA conv (IC % 32 == 0). Returns 1 when gn_part was written,
+// 0 otherwise (the caller must then drop the buffer: nothing initialised
+// it), -1 and launches nothing when x2 and up are both set.
+int airtc_conv2d_mfma(const AirtcConvArgs* a, hipStream_t s);
+// ragged IC: the small-IC kernel up to K = 288, else one thread per output
+void airtc_conv2d_direct(const AirtcConvArgs* a, hipStream_t s);
+// tiny-IC conv (IC <= 4, R*S*IC <= 36; airtc_conv2d_tinyic_ok): lanes along OC
+int airtc_conv2d_tinyic_ok(int IC, int R, int S);
+void airtc_conv2d_tinyic(const AirtcConvArgs* a, hipStream_t s);
 
 // fp8 (MX-scaled MFMA path) -------------------------------------------------
-// conv2d on v_mfma_scale_f32_16x16x128_f8f6f4 (conv2d_fp8.hip). w_fp8 is
-// [OC][K] OCP e4m3 bytes (per-OC host quantization); dq[oc] = a_scale *
-// w_scale[oc] dequantizes in the epilogue; activations quantize in the
-// staging loads (a_scale). Requires IC % 64 == 0; path from
-// airtc_conv2d_splitk_for (nonzero).
+// conv2d on v_mfma_scale_f32_16x16x128_f8f6f4 (conv2d_fp8.hip). dq[oc] =
+// a_scale * w_scale[oc] dequantizes in the epilogue; activations quantize in
+// the staging loads (a_scale). Requires IC % 64 == 0.
 // x_is_q8: x already holds e4m3 codes (u8, producer-quantized by e.g.
-// airtc_group_norm with out_q8) — staging is a raw byte copy, in_aff unused.
+// airtc_group_norm with out_q8): staging is a raw byte copy, in_aff unused.
 // out_q8/out_inv: when non-null and split-K == 1, the epilogue writes e4m3
 // codes q = e4m3(clamp(v / out_scale)) instead of f16 (chained fp8 layers).
-void airtc_conv2d_fp8_mfma(const uint16_t* x, const uint8_t* w_fp8,
-                           const float* dq, const float* bias,
-                           const uint16_t* cbias, const uint16_t* residual,
-                           uint16_t* out, float* ws, int B, int H, int W,
-                           int IC, int HO, int WO, int OC, int R, int S,
-                           int stride, int pad, int act, int path,
-                           const float* in_aff, int in_act, float a_scale,
-                           int x_is_q8, uint8_t* out_q8, float out_inv,
-                           hipStream_t s);
+void airtc_conv2d_fp8_mfma(const AirtcConvArgs* a, const float* dq,
+                           float a_scale, int x_is_q8, uint8_t* out_q8,
+                           float out_inv, hipStream_t s);
 // hardware probes: raw-fragment MX MFMA tile and the fused scale-converts
 // (layout/semantics verified on hardware before the fp8 conv relies on them)
 void airtc_fp8_mx_probe(const uint8_t* A, const uint8_t* B, float* draw,

@@ -60,12 +60,17 @@ def _require_ext():
     return ext
 
 
-def _use_hip(x: torch.Tensor) -> bool:
-    if not x.is_cuda or x.dtype != torch.float16:
+_F16 = (torch.float16,)
+_F16_OR_U8 = (torch.float16, torch.uint8)
+
+
+def _use_hip(x: torch.Tensor, dtypes: tuple | None = _F16) -> bool:
+    """The one "runs on the kernel" predicate: x is on the device, of one of
+    the dtypes the op's kernel takes (None: the op checks dtypes itself), and
+    AIRTC_FORCE_EAGER=1 is not set (read per call)."""
+    if not x.is_cuda or (dtypes is not None and x.dtype not in dtypes):
         return False
-    if os.environ.get("AIRTC_FORCE_EAGER") == "1":
-        return False
-    return True
+    return os.environ.get("AIRTC_FORCE_EAGER") != "1"
 
 
 def uses_hip(x: torch.Tensor) -> bool:
@@ -74,12 +79,113 @@ def uses_hip(x: torch.Tensor) -> bool:
     return _use_hip(x)
 
 
-def _cached(t: torch.Tensor, key: str, build):
-    c = getattr(t, key, None)
-    if c is None:
-        c = build()
-        setattr(t, key, c)
-    return c
+# ---------------------------------------------------------------------------
+# weight caches: tensors derived from a weight, hung on its parameter/module
+# ---------------------------------------------------------------------------
+
+# every attribute name weight_cache has ever set; drop_weight_caches removes
+# exactly these, so a new cache needs no edit anywhere else
+_WEIGHT_CACHE_ATTRS: set = set()
+
+
+def _same_key(a, b) -> bool:
+    """Cache keys: tensors by identity, anything else by value, tuples
+    elementwise."""
+    if isinstance(a, tuple) and isinstance(b, tuple):
+        return len(a) == len(b) and all(map(_same_key, a, b))
+    if a is b:
+        return True
+    if isinstance(a, torch.Tensor) or isinstance(b, torch.Tensor):
+        return False
+    return a == b
+
+
+def weight_cache(owner, name: str, build, key=None):
+    """build() once per owner (a parameter or a module), kept on it as the
+    attribute `name` and recorded in the registry. `key` is whatever else
+    the value was built from (a second tensor, a scale, a device): another
+    key rebuilds. Stored as (key, value)."""
+    _WEIGHT_CACHE_ATTRS.add(name)
+    c = getattr(owner, name, None)
+    if c is None or not _same_key(c[0], key):
+        c = (key, build())
+        setattr(owner, name, c)
+    return c[1]
+
+
+def weight_cache_names() -> frozenset:
+    return frozenset(_WEIGHT_CACHE_ATTRS)
+
+
+def drop_weight_caches(module: torch.nn.Module) -> None:
+    """Remove every weight_cache entry from the module tree and its
+    parameters: call after any in-place weight change."""
+    for m in module.modules():
+        for owner in (m, *m.parameters(recurse=False)):
+            for name in _WEIGHT_CACHE_ATTRS:
+                if hasattr(owner, name):
+                    delattr(owner, name)
+
+
+def _f32(t: torch.Tensor, name: str) -> torch.Tensor:
+    """The contiguous f32 copy of a bias / gamma / beta the kernels read."""
+    return weight_cache(t, name, lambda: t.detach().float().contiguous())
+
+
+def _gemm_layout(weight: torch.Tensor) -> torch.Tensor:
+    """(O,I,R,S) -> the conv kernels' (O, R*S*I) f16 GEMM layout."""
+    return weight_cache(
+        weight, "_airtc_wperm",
+        lambda: weight.detach().permute(0, 2, 3, 1)
+        .reshape(weight.shape[0], -1).contiguous().half())
+
+
+# ---------------------------------------------------------------------------
+# torch reference pieces shared by the CPU / eager paths
+# ---------------------------------------------------------------------------
+
+def _act_ref(y: torch.Tensor, act: int) -> torch.Tensor:
+    if act == ACT_SILU:
+        return F.silu(y)
+    if act == ACT_RELU:
+        return F.relu(y)
+    return y
+
+
+def _in_affine_ref(x: torch.Tensor, in_affine: torch.Tensor,
+                   in_act: int) -> torch.Tensor:
+    """f32 act(x * s + t) with the (B, C, 2) per-channel pairs of in_affine."""
+    aff = in_affine.float()
+    xf = x.float() * aff[:, None, None, :, 0] + aff[:, None, None, :, 1]
+    return _act_ref(xf, in_act)
+
+
+def _epilogue_ref(y, channel_bias, residual, act: int) -> torch.Tensor:
+    """The conv epilogue on an f32 NHWC result (bias already added)."""
+    if channel_bias is not None:
+        y = y + channel_bias.float()[:, None, None, :]
+    if residual is not None:
+        y = y + residual.float()
+    return _act_ref(y, act)
+
+
+def _e4m3(y: torch.Tensor, scale: float) -> torch.Tensor:
+    """float8_e4m3fn codes of y at `scale`, as the kernels encode them:
+    multiply by the f32 reciprocal, clamp to +-448, round to nearest even."""
+    inv = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(
+        scale, dtype=torch.float32)
+    return (y.float() * inv).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+
+
+def _resize_u8_ref(win: torch.Tensor, oh: int, ow: int) -> torch.Tensor:
+    """(h, w, 3) u8 -> (oh, ow, 3) u8, antialiased triangle filter in f32,
+    round-half-even, clamp; an equal-size window comes back as it is."""
+    if tuple(win.shape[:2]) == (oh, ow):
+        return win
+    x = win.permute(2, 0, 1).unsqueeze(0).to(torch.float32)
+    x = F.interpolate(x, size=(oh, ow), mode="bilinear", antialias=True,
+                      align_corners=False)
+    return x.round().clamp(0, 255).to(torch.uint8)[0].permute(1, 2, 0)
 
 
 # ---------------------------------------------------------------------------
@@ -105,23 +211,19 @@ def _tiny_pack(weight: torch.Tensor) -> torch.Tensor:
 def _tail_pack(weight, w_perm, bias, w2, b2):
     """Packed (O, R*S*I + C2) f16 weight and summed f32 bias of a conv with
     a pointwise tail, cached on the conv's weight (`_airtc_wtail`,
-    `_airtc_btail`) together with the tensors they were built from."""
-    c = getattr(weight, "_airtc_wtail", None)
-    if c is None or c[0] is not w2:
-        w2p = _cached(w2, "_airtc_wperm",
-                      lambda: w2.detach().permute(0, 2, 3, 1)
-                      .reshape(w2.shape[0], -1).contiguous().half())
-        c = (w2, torch.cat([w_perm, w2p], dim=1).contiguous())
-        weight._airtc_wtail = c
-    cb = getattr(weight, "_airtc_btail", None)
-    if cb is None or cb[0] is not bias or cb[1] is not b2:
+    `_airtc_btail`) and keyed on the tensors they were built from."""
+    def total_bias():
         parts = [b.detach().float() for b in (bias, b2) if b is not None]
-        tot = None
-        if parts:
-            tot = (parts[0] + parts[1] if len(parts) == 2 else parts[0]).contiguous()
-        cb = (bias, b2, tot)
-        weight._airtc_btail = cb
-    return c[1], cb[2]
+        if not parts:
+            return None
+        return (parts[0] + parts[1] if len(parts) == 2 else parts[0]).contiguous()
+
+    w_tail = weight_cache(
+        weight, "_airtc_wtail",
+        lambda: torch.cat([w_perm, _gemm_layout(w2)], dim=1).contiguous(),
+        key=w2)
+    return w_tail, weight_cache(weight, "_airtc_btail", total_bias,
+                                key=(bias, b2))
 
 
 def conv2d_nhwc(
@@ -208,15 +310,14 @@ def conv2d_nhwc(
         # kernel / the pad route.
         if (I <= 4 and R * S * I <= 36 and in_affine is None
                 and _switch("AIRTC_CONV_TINYIC")):
-            w_tiny = _cached(weight, "_airtc_wtiny", lambda: _tiny_pack(weight))
-            b32 = None
-            if bias is not None:
-                b32 = _cached(bias, "_airtc_b32", lambda: bias.detach().float().contiguous())
             return ext.conv2d_tinyic(
-                x, w_tiny, b32,
-                None if channel_bias is None else channel_bias.contiguous(),
-                None if residual is None else residual.contiguous(),
-                R, S, stride, padding, act)
+                x=x,
+                w_tiny=weight_cache(weight, "_airtc_wtiny",
+                                    lambda: _tiny_pack(weight)),
+                bias=None if bias is None else _f32(bias, "_airtc_b32"),
+                cbias=None if channel_bias is None else channel_bias.contiguous(),
+                residual=None if residual is None else residual.contiguous(),
+                R=R, S=S, stride=stride, pad=padding, act=act)
         # Other small-IC convs at large spatial (and the 3/4-channel conv_in
         # layers with AIRTC_CONV_TINYIC=0) measured 129us at 512² on the
         # scalar small-IC kernel; zero-padding
@@ -226,7 +327,7 @@ def conv2d_nhwc(
         if I < 32 and in_affine is None and x.shape[1] * x.shape[2] >= 16384:
             xp = torch.zeros((*x.shape[:3], 32), dtype=x.dtype, device=x.device)
             xp[..., :I].copy_(x)
-            w_pad = _cached(
+            w_pad = weight_cache(
                 weight,
                 "_airtc_wpad32",
                 lambda: torch.cat(
@@ -238,51 +339,29 @@ def conv2d_nhwc(
                                act=act, residual=residual,
                                channel_bias=channel_bias,
                                stats_groups=stats_groups)
-        w_perm = _cached(
-            weight,
-            "_airtc_wperm",
-            lambda: weight.detach().permute(0, 2, 3, 1).reshape(O, -1).contiguous().half(),
-        )
-        b32 = None
-        if bias is not None:
-            b32 = _cached(bias, "_airtc_b32", lambda: bias.detach().float().contiguous())
+        w_perm = _gemm_layout(weight)
+        b32 = None if bias is None else _f32(bias, "_airtc_b32")
         if x2 is not None:
             # one (O, R*S*I + C2) weight and one summed f32 bias per conv
             # weight, rebuilt if another shortcut is passed with it
             w_perm, b32 = _tail_pack(weight, w_perm, bias, tail[1], tail[2])
-        args = (
-            x,
-            w_perm,
-            b32,
-            None if channel_bias is None else channel_bias.contiguous(),
-            None if residual is None else residual.contiguous(),
-            R,
-            S,
-            stride,
-            padding,
-            act,
-            None if in_affine is None else in_affine.contiguous(),
-            in_act,
-        )
-        if x2 is not None or upsample2x:
-            args = args + (x2, upsample2x)
-        if stats_groups and act == ACT_NONE:
-            y, part = ext.conv2d_stats(*args[:12], stats_groups, *args[12:])
-            if part is not None:
-                # (partials, G, version): the norm ignores them if the
-                # tensor was written in place after the conv
-                y._airtc_gn_part = (part, stats_groups, y._version)
-            return y
-        return ext.conv2d(*args)
+        want_stats = bool(stats_groups) and act == ACT_NONE
+        y, part = ext.conv2d(
+            x=x, w_perm=w_perm, bias=b32,
+            cbias=None if channel_bias is None else channel_bias.contiguous(),
+            residual=None if residual is None else residual.contiguous(),
+            R=R, S=S, stride=stride, pad=padding, act=act,
+            in_affine=None if in_affine is None else in_affine.contiguous(),
+            in_act=in_act, stats_groups=stats_groups if want_stats else 0,
+            x2=x2, upsample2x=upsample2x)
+        if part is not None:
+            # (partials, G, version): the norm ignores them if the tensor
+            # was written in place after the conv
+            y._airtc_gn_part = (part, stats_groups, y._version)
+        return y
 
     if in_affine is not None:
-        aff = in_affine.float()
-        xf = x.float() * aff[:, None, None, :, 0] + aff[:, None, None, :, 1]
-        if in_act == ACT_SILU:
-            xf = F.silu(xf)
-        elif in_act == ACT_RELU:
-            xf = F.relu(xf)
-        x = xf.to(x.dtype)
+        x = _in_affine_ref(x, in_affine, in_act).to(x.dtype)
     xc = x.permute(0, 3, 1, 2)
     if upsample2x:
         xc = F.interpolate(xc, scale_factor=2, mode="nearest")
@@ -292,15 +371,7 @@ def conv2d_nhwc(
         x2, w2, b2 = tail
         y = y + F.conv2d(x2.permute(0, 3, 1, 2).float(), w2.float(),
                          None if b2 is None else b2.float())
-    y = y.permute(0, 2, 3, 1)
-    if channel_bias is not None:
-        y = y + channel_bias.float()[:, None, None, :]
-    if residual is not None:
-        y = y + residual.float()
-    if act == ACT_SILU:
-        y = F.silu(y)
-    elif act == ACT_RELU:
-        y = F.relu(y)
+    y = _epilogue_ref(y.permute(0, 2, 3, 1), channel_bias, residual, act)
     return y.to(x.dtype).contiguous()
 
 
@@ -330,10 +401,7 @@ def fp8_roundtrip(x: torch.Tensor, scale: float) -> torch.Tensor:
     e4m3(clamp(x * (1/scale), +-448)) * scale — the kernel multiplies by the
     f32 reciprocal (v_cvt_pk_fp8_f32 path), so the emulation does too.
     Reference for tests and the CPU path (f32 in/out)."""
-    inv = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(
-        scale, dtype=torch.float32)
-    q = (x.float() * inv).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
-    return q.to(torch.float32) * scale
+    return _e4m3(x, scale).to(torch.float32) * scale
 
 
 def conv2d_fp8_nhwc(
@@ -367,38 +435,21 @@ def conv2d_fp8_nhwc(
     Requires IC % 64 == 0 (use conv2d_nhwc for other layers)."""
     O, I, R, S = weight.shape
     x_q8 = x.dtype == torch.uint8
-    if _use_hip(x) or (x_q8 and x.is_cuda
-                       and os.environ.get("AIRTC_FORCE_EAGER") != "1"):
+    if _use_hip(x, _F16_OR_U8):
         ext = _require_ext()
-        wq = getattr(weight, "_airtc_wfp8", None)
-        if wq is None:
-            wq = quantize_weight_fp8(weight)
-            weight._airtc_wfp8 = wq
-        w_fp8, w_scale = wq
-        dq = getattr(weight, "_airtc_wdq", None)
-        if dq is None or dq[0] != a_scale:
-            dq = (a_scale, (w_scale * a_scale).contiguous())
-            weight._airtc_wdq = dq
-        b32 = None
-        if bias is not None:
-            b32 = _cached(bias, "_airtc_b32", lambda: bias.detach().float().contiguous())
+        w_fp8, w_scale = weight_cache(weight, "_airtc_wfp8",
+                                      lambda: quantize_weight_fp8(weight))
+        dq = weight_cache(weight, "_airtc_wdq",
+                          lambda: (w_scale * a_scale).contiguous(), key=a_scale)
         return ext.conv2d_fp8(
-            x,
-            w_fp8,
-            dq[1],
-            a_scale,
-            b32,
-            None if channel_bias is None else channel_bias.contiguous(),
-            None if residual is None else residual.contiguous(),
-            R,
-            S,
-            stride,
-            padding,
-            act,
-            None if in_affine is None else in_affine.contiguous(),
-            in_act,
-            0.0 if out_fp8_scale is None else out_fp8_scale,
-        )
+            x=x, w_fp8=w_fp8, dq=dq, a_scale=a_scale,
+            bias=None if bias is None else _f32(bias, "_airtc_b32"),
+            cbias=None if channel_bias is None else channel_bias.contiguous(),
+            residual=None if residual is None else residual.contiguous(),
+            R=R, S=S, stride=stride, pad=padding, act=act,
+            in_affine=None if in_affine is None else in_affine.contiguous(),
+            in_act=in_act,
+            out_scale=0.0 if out_fp8_scale is None else out_fp8_scale)
 
     # emulation path (CPU tests + GPU numerics golden): quantize exactly as
     # the kernel does, then run the f32 reference conv
@@ -406,15 +457,8 @@ def conv2d_fp8_nhwc(
         assert in_affine is None, "pre-quantized input excludes input affine"
         xq = x.view(torch.float8_e4m3fn).to(torch.float32) * a_scale
     else:
-        if in_affine is not None:
-            aff = in_affine.float()
-            xf = x.float() * aff[:, None, None, :, 0] + aff[:, None, None, :, 1]
-            if in_act == ACT_SILU:
-                xf = F.silu(xf)
-            elif in_act == ACT_RELU:
-                xf = F.relu(xf)
-        else:
-            xf = x.float()
+        xf = x.float() if in_affine is None \
+            else _in_affine_ref(x, in_affine, in_act)
         xq = fp8_roundtrip(xf, a_scale)
     w_fp8, w_scale = quantize_weight_fp8(weight)
     wdec = w_fp8.view(torch.float8_e4m3fn).to(torch.float32) * w_scale[:, None]
@@ -422,19 +466,9 @@ def conv2d_fp8_nhwc(
     y = F.conv2d(xq.permute(0, 3, 1, 2), wdec,
                  None if bias is None else bias.float(),
                  stride=stride, padding=padding).permute(0, 2, 3, 1)
-    if channel_bias is not None:
-        y = y + channel_bias.float()[:, None, None, :]
-    if residual is not None:
-        y = y + residual.float()
-    if act == ACT_SILU:
-        y = F.silu(y)
-    elif act == ACT_RELU:
-        y = F.relu(y)
+    y = _epilogue_ref(y, channel_bias, residual, act)
     if out_fp8_scale is not None:
-        inv = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(
-            out_fp8_scale, dtype=torch.float32)
-        q = (y.float() * inv).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
-        return q.view(torch.uint8).contiguous()
+        return _e4m3(y, out_fp8_scale).view(torch.uint8).contiguous()
     # u8 input carries no output dtype — use the model (weight) dtype
     return y.to(weight.dtype if x_q8 else x.dtype).contiguous()
 
@@ -457,10 +491,9 @@ def group_norm_coeffs(
     if _use_hip(x):
         if (x.shape[-1] // num_groups) % 2 != 0:
             raise ValueError("group_norm kernel needs even channels-per-group")
-        ext = _require_ext()
-        g32 = _cached(gamma, "_airtc_g32", lambda: gamma.detach().float().contiguous())
-        b32 = _cached(beta, "_airtc_b32", lambda: beta.detach().float().contiguous())
-        return ext.group_norm_coeffs(x, num_groups, g32, b32, eps)
+        return _require_ext().group_norm_coeffs(
+            x, num_groups, _f32(gamma, "_airtc_g32"), _f32(beta, "_airtc_b32"),
+            eps)
     b, c = x.shape[0], x.shape[-1]
     xf = x.reshape(b, -1, num_groups, c // num_groups).permute(0, 2, 1, 3).float()
     mean = xf.mean(dim=(2, 3))                             # (B, G)
@@ -494,8 +527,7 @@ def group_norm_silu_nhwc(
                 f"C={x.shape[-1]} groups={num_groups}"
             )
         ext = _require_ext()
-        g32 = _cached(gamma, "_airtc_g32", lambda: gamma.detach().float().contiguous())
-        b32 = _cached(beta, "_airtc_b32", lambda: beta.detach().float().contiguous())
+        g32, b32 = _f32(gamma, "_airtc_g32"), _f32(beta, "_airtc_b32")
         act = ACT_SILU if silu else ACT_NONE
         # partial statistics the producing conv's finalize left on x
         # (conv2d_nhwc stats_groups): same tensor, same G, unmodified since
@@ -514,10 +546,7 @@ def group_norm_silu_nhwc(
     if silu:
         y = F.silu(y)
     if fp8_scale is not None:
-        inv = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(
-            fp8_scale, dtype=torch.float32)
-        q = (y.float() * inv).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
-        return q.view(torch.uint8).contiguous()
+        return _e4m3(y, fp8_scale).view(torch.uint8).contiguous()
     return y.to(x.dtype).contiguous()
 
 
@@ -526,10 +555,8 @@ def layer_norm(
 ) -> torch.Tensor:
     # the kernel reads 8 channels per lane; other widths take the torch path
     if _use_hip(x) and x.shape[-1] % 8 == 0:
-        ext = _require_ext()
-        g32 = _cached(gamma, "_airtc_g32", lambda: gamma.detach().float().contiguous())
-        b32 = _cached(beta, "_airtc_b32", lambda: beta.detach().float().contiguous())
-        return ext.layer_norm(x, g32, b32, eps)
+        return _require_ext().layer_norm(
+            x, _f32(gamma, "_airtc_g32"), _f32(beta, "_airtc_b32"), eps)
     return F.layer_norm(x.float(), (x.shape[-1],), gamma.float(), beta.float(), eps).to(x.dtype)
 
 
@@ -605,14 +632,12 @@ def linear(
             and _use_hip(x) and x.dim() == 3 and weight.shape[1] % 32 == 0:
         ext = _require_ext()
         b, l, c = x.shape
-        b32 = None
-        if bias is not None:
-            b32 = _cached(bias, "_airtc_b32", lambda: bias.detach().float().contiguous())
-        w16 = _cached(weight, "_airtc_w16", lambda: weight.detach().contiguous().half())
-        y = ext.conv2d(
-            x.reshape(b, l, 1, c), w16, b32, None,
-            residual.reshape(b, l, 1, -1).contiguous(), 1, 1, 1, 0, ACT_NONE,
-        )
+        w16 = weight_cache(weight, "_airtc_w16",
+                           lambda: weight.detach().contiguous().half())
+        y, _ = ext.conv2d(
+            x=x.reshape(b, l, 1, c), w_perm=w16,
+            bias=None if bias is None else _f32(bias, "_airtc_b32"),
+            residual=residual.reshape(b, l, 1, -1).contiguous(), R=1, S=1)
         return y.reshape(b, l, -1)
     if residual is not None and _use_hip(x) \
             and os.environ.get("AIRTC_LT_EPILOGUE") != "0":
@@ -682,12 +707,7 @@ def add_act(a: torch.Tensor, b: torch.Tensor, act: int = ACT_NONE) -> torch.Tens
     """Fused residual add + optional activation (TAESD add+relu, resnet skips)."""
     if _use_hip(a) and a.numel() % 8 == 0:
         return _require_ext().add_act(a, b, act)
-    y = a.float() + b.float()
-    if act == ACT_SILU:
-        y = F.silu(y)
-    elif act == ACT_RELU:
-        y = F.relu(y)
-    return y.to(a.dtype)
+    return _act_ref(a.float() + b.float(), act).to(a.dtype)
 
 
 # ---------------------------------------------------------------------------
@@ -838,8 +858,8 @@ def preprocess_from_u8(frame_u8: torch.Tensor, dtype: torch.dtype) -> torch.Tens
     """
     if frame_u8.dim() == 3:
         frame_u8 = frame_u8.unsqueeze(0)
-    if frame_u8.is_cuda and dtype == torch.float16 and hip_ext() is not None \
-            and os.environ.get("AIRTC_FORCE_EAGER") != "1":
+    if dtype == torch.float16 and _use_hip(frame_u8, None) \
+            and hip_ext() is not None:
         return _require_ext().preprocess_u8(frame_u8.contiguous())
     return (frame_u8.to(torch.float32) / 127.5 - 1.0).to(dtype)
 
@@ -914,18 +934,13 @@ def fit_frame_u8(src: torch.Tensor, out: torch.Tensor, slot: int,
     H, W = out.shape[1], out.shape[2]
     (y0, x0, ch, cw), (oy, ox, oh, ow) = fit_geometry(
         src.shape[0], src.shape[1], H, W, mode)
-    if src.is_cuda and os.environ.get("AIRTC_FORCE_EAGER") != "1":
+    if _use_hip(src, None):
         if not out.is_contiguous():
             raise ValueError("out must be contiguous (it is written in place)")
         _require_ext().fit_resize_u8(src.contiguous(), out, slot, y0, x0, ch,
                                      cw, oy, ox, oh, ow)
         return
-    win = src[y0:y0 + ch, x0:x0 + cw]
-    if (ch, cw) != (oh, ow):
-        x = win.permute(2, 0, 1).unsqueeze(0).to(torch.float32)
-        x = F.interpolate(x, size=(oh, ow), mode="bilinear", antialias=True,
-                          align_corners=False)
-        win = x.round().clamp(0, 255).to(torch.uint8)[0].permute(1, 2, 0)
+    win = _resize_u8_ref(src[y0:y0 + ch, x0:x0 + cw], oh, ow)
     dst = out[slot]
     if (oh, ow) != (H, W):
         dst.zero_()
@@ -1087,7 +1102,7 @@ def canny_hint(frames_u8: torch.Tensor, thr, reach: int = 16,
         raise ValueError(
             f"out must be a contiguous {dtype} {tuple(frames_u8.shape)} tensor "
             f"on {frames_u8.device}")
-    if _on_kernel(frames_u8):
+    if _use_hip(frames_u8, None):
         if out is None:
             out = torch.empty(frames_u8.shape, dtype=dtype, device=frames_u8.device)
         return _require_ext().canny_hint(
@@ -1168,10 +1183,6 @@ def _check_rgb_for_i420(x: torch.Tensor, dtype: torch.dtype | None) -> None:
         raise ValueError(f"I420 needs even H, W >= 2, got {h}x{w}")
 
 
-def _on_kernel(x: torch.Tensor) -> bool:
-    return x.is_cuda and os.environ.get("AIRTC_FORCE_EAGER") != "1"
-
-
 def _clip8(v: torch.Tensor) -> torch.Tensor:
     return v.clamp(0, 255).to(torch.uint8)
 
@@ -1244,7 +1255,7 @@ def rgb_u8_to_i420(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Te
     b, h, w, _ = xb.shape
     ob = None if out is None else (out.unsqueeze(0) if squeeze else out)
     _check_out(ob, x, (b, h // 2 * 3, w))
-    if _on_kernel(x):
+    if _use_hip(x, None):
         res = _require_ext().rgb_u8_to_i420(xb.contiguous(), ob)
     else:
         res = _rgb_u8_to_i420_ref(xb)
@@ -1340,7 +1351,7 @@ def unfit_frame_u8(img: torch.Tensor, window, size, fmt: str = "rgb",
         raise ValueError(f"I420 needs even H, W >= 2, got {Ht}x{Wt}")
     shape = (Ht, Wt, 3) if fmt == "rgb" else (Ht // 2 * 3, Wt)
     _check_out(out, img, shape)
-    if _on_kernel(img):
+    if _use_hip(img, None):
         if not img.is_contiguous():
             raise ValueError("img must be contiguous")
         if out is None:
@@ -1351,12 +1362,7 @@ def unfit_frame_u8(img: torch.Tensor, window, size, fmt: str = "rgb",
         else:
             _require_ext().fit_resize_u8_i420(img, out, ry, rx, rh, rw)
         return out
-    win = img[ry:ry + rh, rx:rx + rw]
-    if (rh, rw) != (Ht, Wt):
-        x = win.permute(2, 0, 1).unsqueeze(0).to(torch.float32)
-        x = F.interpolate(x, size=(Ht, Wt), mode="bilinear", antialias=True,
-                          align_corners=False)
-        win = x.round().clamp(0, 255).to(torch.uint8)[0].permute(1, 2, 0)
+    win = _resize_u8_ref(img[ry:ry + rh, rx:rx + rw], Ht, Wt)
     # contiguous, and never a view of img
     res = win.clone(memory_format=torch.contiguous_format)
     if fmt == "i420":
@@ -1380,7 +1386,7 @@ def i420_to_rgb_u8(x: torch.Tensor, H: int | None = None,
     xb, squeeze = _batched(x, 2)
     ob = None if out is None else (out.unsqueeze(0) if squeeze else out)
     _check_out(ob, x, (xb.shape[0], h, w, 3))
-    if _on_kernel(x):
+    if _use_hip(x, None):
         res = _require_ext().i420_to_rgb_u8(xb.contiguous(), ob)
     else:
         res = _i420_to_rgb_u8_ref(xb)

@@ -176,7 +176,8 @@ def bench_conv_operands(iters, reps=9):
         wt, b32 = ops.interface._tiny_pack(w), b.float()
         ext = ops.hip_ext()
         new = (lambda x=x, wt=wt, b32=b32:
-               ext.conv2d_tinyic(x, wt, b32, None, None, 3, 3, 1, 1, 0))
+               ext.conv2d_tinyic(x=x, w_tiny=wt, bias=b32, R=3, S=3, stride=1,
+                                 pad=1))
         cases.append((f"conv_in {hw}x{hw} {ic}->{oc}", old, new))
 
     print("== conv operands in place (old = the kernels replaced, new = one "
