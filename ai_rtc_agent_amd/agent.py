@@ -364,6 +364,12 @@ async def on_startup(app: web.Application) -> None:
         if cfg.controlnet_processor != "none":
             # a conditioning processor is only ever wanted with its ControlNet
             cfg.use_controlnet = True
+        for key in ("safety_checker", "safety_adjustment"):
+            if app.get(key) is not None:
+                setattr(cfg, key, app[key])
+        if app.get("safety_checker") or os.environ.get("AIRTC_SAFETY_CHECKER"):
+            # naming a checker (flag or environment) switches the gate on
+            cfg.use_safety_checker = True
         cfg.__post_init__()  # validate what was set after construction
         st["pool"] = PipelinePool.create(
             model_id=app["model_id"], n_gpus=app["n_gpus"], cfg=cfg,
@@ -411,6 +417,8 @@ def create_app(
     canny_low: Optional[int] = None,
     canny_high: Optional[int] = None,
     canny_reach: Optional[int] = None,
+    safety_checker: Optional[str] = None,
+    safety_adjustment: Optional[float] = None,
 ) -> web.Application:
     app = web.Application(middlewares=[cors_middleware])
     app["model_id"] = model_id
@@ -432,6 +440,11 @@ def create_app(
     app["canny_low"] = canny_low
     app["canny_high"] = canny_high
     app["canny_reach"] = canny_reach
+    # None: EngineConfig defaults (AIRTC_SAFETY_CHECKER, AIRTC_SAFETY_ADJUSTMENT);
+    # naming a checker switches the output gate on. Deliberately not part of
+    # the runtime config: a publisher must not relax its own gate
+    app["safety_checker"] = safety_checker
+    app["safety_adjustment"] = safety_adjustment
     app["state"] = {
         "pcs": set(),
         "source_track": None,
@@ -522,6 +535,20 @@ def main() -> None:
                         help="how many 3x3 steps a weak edge may lie from a "
                              "strong one, 0..32; cv2.Canny's hysteresis is "
                              "unbounded (default: $AIRTC_CANNY_REACH or 16)")
+    parser.add_argument("--safety-checker", default=None,
+                        choices=["tiny", "clip"],
+                        help="gate every returned frame with a safety "
+                             "checker and send black for a flagged one: "
+                             "clip = the CLIP ViT-L/14 "
+                             "StableDiffusionSafetyChecker, run inside the "
+                             "captured decode graph; tiny = the small conv "
+                             "classifier (default: $AIRTC_SAFETY_CHECKER, "
+                             "else no checker)")
+    parser.add_argument("--safety-adjustment", type=float, default=None,
+                        help="added to every clip checker score, positive is "
+                             "stricter; operator-only, not reachable from "
+                             "POST /config (default: "
+                             "$AIRTC_SAFETY_ADJUSTMENT or 0)")
     parser.add_argument("--streams-per-gpu", type=int, default=1,
                         help="multi-stream batched serving: sessions per "
                              "GPU batched through one engine (fbs=K; "
@@ -565,7 +592,9 @@ def main() -> None:
                           ("controlnet_scale", "AIRTC_CONTROLNET_SCALE"),
                           ("canny_low", "AIRTC_CANNY_LOW"),
                           ("canny_high", "AIRTC_CANNY_HIGH"),
-                          ("canny_reach", "AIRTC_CANNY_REACH")):
+                          ("canny_reach", "AIRTC_CANNY_REACH"),
+                          ("safety_checker", "AIRTC_SAFETY_CHECKER"),
+                          ("safety_adjustment", "AIRTC_SAFETY_ADJUSTMENT")):
             if getattr(args, flag) is not None:
                 os.environ[env] = str(getattr(args, flag))
         fe = WorkerFrontend(args.workers, model_id=args.model_id,
@@ -587,7 +616,9 @@ def main() -> None:
                      controlnet_processor=args.controlnet_processor,
                      controlnet_scale=args.controlnet_scale,
                      canny_low=args.canny_low, canny_high=args.canny_high,
-                     canny_reach=args.canny_reach)
+                     canny_reach=args.canny_reach,
+                     safety_checker=args.safety_checker,
+                     safety_adjustment=args.safety_adjustment)
     web.run_app(app, host=args.host, port=args.port)
 
 

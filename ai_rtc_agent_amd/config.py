@@ -9,6 +9,7 @@ canonical config (reference lib/pipeline.py:11-14, lib/wrapper.py:46-65).
 """
 from __future__ import annotations
 
+import math
 import os
 from dataclasses import dataclass, field
 from typing import List, Optional
@@ -69,6 +70,15 @@ def _env_float(name: str, default: float) -> float:
 # AIRTC_CANNY_REACH (0..32)           -> EngineConfig.canny_reach: how many
 #                                        3x3 steps a weak edge may lie from a
 #                                        strong one
+# AIRTC_SAFETY_CHECKER (tiny|clip)    -> EngineConfig.safety_checker: which
+#                                        checker use_safety_checker builds;
+#                                        clip = the reference's CLIP ViT-L/14
+#                                        StableDiffusionSafetyChecker. The
+#                                        agent switches the checker on when
+#                                        this (or --safety-checker) is set
+# AIRTC_SAFETY_ADJUSTMENT (float)     -> EngineConfig.safety_adjustment: added
+#                                        to every clip score, positive is
+#                                        stricter
 
 
 def engines_cache_dir() -> str:
@@ -111,6 +121,7 @@ def media_yuv() -> bool:
 OUTPUT_FORMATS = ("rgb", "i420")
 OUTPUT_SIZES = ("engine", "source")
 CONTROLNET_PROCESSORS = ("none", "canny")
+SAFETY_CHECKERS = ("tiny", "clip")
 
 
 @dataclass
@@ -166,6 +177,16 @@ class EngineConfig:
     use_controlnet: bool = False
     controlnet_scale: float = field(default_factory=lambda: _env_float("AIRTC_CONTROLNET_SCALE", 1.0))
     use_safety_checker: bool = False
+    # which checker use_safety_checker builds: "tiny" = the small conv
+    # classifier (models/safety.py), "clip" = the reference's
+    # StableDiffusionSafetyChecker (models/safety_clip.py: CLIP ViT-L/14
+    # image tower, cosine against concept embeddings), run inside the
+    # captured decode graph. safety_adjustment is that checker's
+    # `adjustment`, added to every score (positive is stricter); per serving
+    # slot at run time through engine.update_safety, which is deliberately
+    # not reachable from POST /config or the datachannel.
+    safety_checker: str = field(default_factory=lambda: os.environ.get("AIRTC_SAFETY_CHECKER") or "tiny")
+    safety_adjustment: float = field(default_factory=lambda: _env_float("AIRTC_SAFETY_ADJUSTMENT", 0.0))
     similarity_filter: SimilarityFilterConfig = field(default_factory=SimilarityFilterConfig)
     encoder: EncoderConfig = field(default_factory=EncoderConfig)
     device: str = "cuda"
@@ -234,6 +255,16 @@ class EngineConfig:
     canny_reach: int = field(default_factory=lambda: _env_int("AIRTC_CANNY_REACH", 16))
 
     def __post_init__(self) -> None:
+        if self.safety_checker not in SAFETY_CHECKERS:
+            raise ValueError(
+                f"safety_checker must be one of {SAFETY_CHECKERS}, "
+                f"got {self.safety_checker!r}")
+        if isinstance(self.safety_adjustment, bool) \
+                or not isinstance(self.safety_adjustment, (int, float)) \
+                or not math.isfinite(self.safety_adjustment):
+            raise ValueError(
+                f"safety_adjustment must be a finite number, got "
+                f"{self.safety_adjustment!r}")
         if self.controlnet_processor not in CONTROLNET_PROCESSORS:
             raise ValueError(
                 f"controlnet_processor must be one of {CONTROLNET_PROCESSORS}, "

@@ -24,6 +24,7 @@ from __future__ import annotations
 from typing import Optional, Sequence
 
 import contextlib
+import dataclasses
 import logging
 import math
 import os
@@ -57,6 +58,7 @@ class StreamDiffusionEngine:
         unet: Optional[UNet2DCondition] = None,
         vae: Optional[TinyVAE] = None,
         text_encoder: Optional[TextEncoder] = None,
+        safety_checker: Optional[torch.nn.Module] = None,
     ) -> None:
         self.cfg = cfg
         if cfg.output_format not in ("rgb", "i420"):
@@ -122,7 +124,16 @@ class StreamDiffusionEngine:
 
             self.controlnet = ControlNet(ucfg)
         self.safety_checker = None
-        if cfg.use_safety_checker:
+        # safety_checker="clip": the reference's CLIP checker, decided and
+        # applied on the device inside the decode graph (_decode_core)
+        self._clip_safety = False
+        if cfg.use_safety_checker and cfg.safety_checker == "clip":
+            from ..models.safety_clip import ClipSafetyChecker
+
+            self.safety_checker = (safety_checker if safety_checker is not None
+                                   else ClipSafetyChecker())
+            self._clip_safety = True
+        elif cfg.use_safety_checker:
             from ..models.safety import SafetyChecker
 
             self.safety_checker = SafetyChecker()
@@ -130,6 +141,16 @@ class StreamDiffusionEngine:
         # real weights when available: model_id as a local diffusers-style
         # dir, or an HF-cache snapshot (random init otherwise — offline)
         self._load_weights_if_present(cfg.model_id)
+        if self._clip_safety:
+            from ..models.load import load_safety_checker_if_present
+
+            # the checker's own repository in the HF cache, when the model
+            # directory brought none
+            load_safety_checker_if_present(self.safety_checker)
+            if self.safety_checker.weights != "loaded":
+                logging.getLogger(__name__).warning(
+                    "safety checker: no checkpoint found, the CLIP checker "
+                    "runs on random weights and its verdicts mean nothing")
 
         # LoRA fusion happens BEFORE device placement / graph capture
         # (reference fuses before TRT compile, lib/wrapper.py:645-697).
@@ -268,6 +289,16 @@ class StreamDiffusionEngine:
             self._canny_thr = torch.tensor(
                 [[cfg.canny_low, cfg.canny_high]] * fbs, dtype=torch.int32).to(dev)
         self.rcfg.reset(self._init_noise)
+        # clip safety checker: the per-slot adjustment the head kernel reads
+        # from memory and the per-slot count of flagged frames it keeps
+        # (read back only by stats()); the counts outlive a re-prepare
+        self._safety_adjust = None
+        if self._clip_safety:
+            self._safety_adjust = torch.full(
+                (fbs,), float(cfg.safety_adjustment), dtype=torch.float32).to(dev)
+            cnt = getattr(self, "_safety_count", None)
+            if cnt is None or cnt.shape[0] != fbs:
+                self._safety_count = torch.zeros(fbs, dtype=torch.int32, device=dev)
 
         # static I/O buffers (graph-stable addresses); _frame_in (u8) is the
         # only per-frame input — preprocess lives inside the graph
@@ -362,7 +393,8 @@ class StreamDiffusionEngine:
         """After any in-place weight change: drop the lazily-built GPU weight
         transforms (conv GEMM layouts, fused QKV, f32 bias copies), re-sync
         replicas, and force a graph re-capture."""
-        for module in (self.unet, self.vae, self.controlnet):
+        for module in (self.unet, self.vae, self.controlnet,
+                       self.safety_checker if self._clip_safety else None):
             if module is not None:
                 ops.drop_weight_caches(module)
         from ..parallel.collectives import broadcast_engine_weights
@@ -408,6 +440,8 @@ class StreamDiffusionEngine:
         if getattr(self, "_canny", False):
             d["canny_low"] = int(cfg.canny_low)
             d["canny_high"] = int(cfg.canny_high)
+        if self._clip_safety:
+            d["safety_adjustment"] = float(cfg.safety_adjustment)
         return d
 
     def _set_ctl(self, slot: Optional[int], **kw) -> None:
@@ -620,6 +654,41 @@ class StreamDiffusionEngine:
         if slot is None:
             self.cfg.canny_low, self.cfg.canny_high = default
 
+    @torch.no_grad()
+    def update_safety(self, adjustment: float, slot: Optional[int] = None) -> None:
+        """Change the clip safety checker's adjustment (added to every score,
+        positive is stricter) of one serving slot, or of every slot and the
+        replica default: an in-place write of the (fbs,) f32 tensor the head
+        kernel reads from memory, never a re-capture. Operator-only: it is
+        not reachable from POST /config or the datachannel, a publisher
+        must not be able to relax its own gate."""
+        self._check_slot(slot)
+        if not self._clip_safety:
+            raise ValueError(
+                "update_safety needs use_safety_checker with safety_checker='clip'")
+        if isinstance(adjustment, bool) or not isinstance(adjustment, (int, float)) \
+                or not math.isfinite(adjustment):
+            raise ValueError(f"adjustment must be a finite number, got {adjustment!r}")
+        adj = float(adjustment)
+        fbs = self.cfg.frame_buffer_size
+        rows = torch.full((fbs if slot is None else 1,), adj,
+                          dtype=torch.float32).to(self.device)
+        dst = self._safety_adjust if slot is None else self._safety_adjust[slot:slot + 1]
+        if (self.device.type == "cuda" and self._graph is not None
+                and self._pipelined):
+            # the decode graph replays on stream B: order the write there,
+            # as _row_writes does on stream A for the denoise graph's rows
+            cur = torch.cuda.current_stream()
+            with torch.cuda.stream(self._sB):
+                self._sB.wait_stream(cur)
+                rows.record_stream(self._sB)
+                dst.copy_(rows)
+        else:
+            dst.copy_(rows)
+        self._set_ctl(slot, safety_adjustment=adj)
+        if slot is None:
+            self.cfg.safety_adjustment = adj
+
     def _reprepare(self, guidance_scale: Optional[float] = None,
                    delta: Optional[float] = None,
                    t_index_list: Optional[list] = None) -> None:
@@ -656,6 +725,8 @@ class StreamDiffusionEngine:
             if self._canny and (c["canny_low"], c["canny_high"]) != (
                     old["canny_low"], old["canny_high"]):
                 self.update_canny(c["canny_low"], c["canny_high"], slot)
+            if self._clip_safety and c["safety_adjustment"] != old["safety_adjustment"]:
+                self.update_safety(c["safety_adjustment"], slot)
 
     @staticmethod
     def _tensors_of(coeff: dict) -> list:
@@ -724,6 +795,8 @@ class StreamDiffusionEngine:
         if self._canny and (c["canny_low"], c["canny_high"]) != (
                 d["canny_low"], d["canny_high"]):
             self.update_canny(d["canny_low"], d["canny_high"], slot)
+        if self._clip_safety and c["safety_adjustment"] != d["safety_adjustment"]:
+            self.update_safety(d["safety_adjustment"], slot)
         self._prev_out = None
         self._prev_sizes = None
         if slot < len(self._out_size):
@@ -1003,7 +1076,13 @@ class StreamDiffusionEngine:
     @torch.no_grad()
     def _decode_core(self, latent: torch.Tensor) -> torch.Tensor:
         decoded = self.vae.decode(latent)
-        if self.safety_checker is not None:
+        if self._clip_safety:
+            # patches -> tower -> head -> black, all on the device and in
+            # the decoder's image, so RGB, I420 and source-size egress
+            # inherit the verdict
+            decoded = self.safety_checker.filter_(
+                decoded.contiguous(), self._safety_adjust, self._safety_count)
+        elif self.safety_checker is not None:
             decoded = self.safety_checker.filter(decoded)
         if self.cfg.output_format == "i420" and not self._egress:
             # same launch count: the u8 rounding and the colour conversion
@@ -1057,10 +1136,15 @@ class StreamDiffusionEngine:
         # warmup (weight-transform caches etc.) on a side stream
         sA.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(sA):
+            # the warmup decodes are nobody's frames: keep them out of the
+            # clip checker's flagged-frame counts
+            counts = self._safety_count.clone() if self._clip_safety else None
             for _ in range(2):
                 lat = self._denoise_core()
                 self._lat_out[0].copy_(lat)
                 _ = self._decode_core(self._lat_out[0])
+            if counts is not None:
+                self._safety_count.copy_(counts)
         torch.cuda.current_stream().wait_stream(sA)
 
         if not self._pipelined:
@@ -1387,6 +1471,17 @@ class StreamDiffusionEngine:
                 # [low, high] per slot, as last written
                 "canny_thresholds": [
                     [c["canny_low"], c["canny_high"]] for c in self._slot_ctl],
+            }
+        if self._clip_safety and getattr(self, "_safety_adjust", None) is not None:
+            d["safety"] = {
+                "arch": "clip-vit",
+                "config": dataclasses.asdict(self.safety_checker.cfg),
+                "weights": self.safety_checker.weights,
+                # per slot, as last written (host-side copies)
+                "adjustment": [c["safety_adjustment"] for c in self._slot_ctl],
+                # per slot; the one device read, made here and never in the
+                # frame path
+                "frames_flagged": self._safety_count.tolist(),
             }
         if self.cfg.use_fp8:
             d["fp8"] = {

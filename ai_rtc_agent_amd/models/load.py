@@ -326,6 +326,113 @@ def load_clip_text_encoder(model, sd: Dict[str, torch.Tensor],
     return n
 
 
+# ---------------------------------------------------------------------------
+# CLIP safety checker (CompVis/stable-diffusion-safety-checker; the
+# safety_checker/ folder of SD1.5 snapshots). ClipSafetyChecker carries the
+# checkpoint's own parameter names, so the map is name -> shape.
+# ---------------------------------------------------------------------------
+SAFETY_CHECKER_REPO = "CompVis/stable-diffusion-safety-checker"
+
+
+def safety_checker_key_map(cfg=None) -> Dict[str, Tuple[int, ...]]:
+    """Every tensor of a StableDiffusionSafetyChecker checkpoint for `cfg`
+    (default: the published ViT-L/14 one), name -> shape."""
+    from .safety_clip import ClipSafetyConfig
+
+    cfg = cfg or ClipSafetyConfig()
+    h, vt = cfg.hidden, "vision_model.vision_model"
+    keys: Dict[str, Tuple[int, ...]] = {
+        f"{vt}.embeddings.class_embedding": (h,),
+        f"{vt}.embeddings.patch_embedding.weight": (h, 3, cfg.patch, cfg.patch),
+        f"{vt}.embeddings.position_embedding.weight": (cfg.tokens, h),
+        "visual_projection.weight": (cfg.projection, h),
+        "concept_embeds": (cfg.concepts, cfg.projection),
+        "special_care_embeds": (cfg.special, cfg.projection),
+        "concept_embeds_weights": (cfg.concepts,),
+        "special_care_embeds_weights": (cfg.special,),
+    }
+    for norm in ("pre_layrnorm", "post_layernorm"):
+        keys[f"{vt}.{norm}.weight"] = keys[f"{vt}.{norm}.bias"] = (h,)
+    for i in range(cfg.layers):
+        p = f"{vt}.encoder.layers.{i}"
+        for norm in ("layer_norm1", "layer_norm2"):
+            keys[f"{p}.{norm}.weight"] = keys[f"{p}.{norm}.bias"] = (h,)
+        for proj in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            keys[f"{p}.self_attn.{proj}.weight"] = (h, h)
+            keys[f"{p}.self_attn.{proj}.bias"] = (h,)
+        keys[f"{p}.mlp.fc1.weight"], keys[f"{p}.mlp.fc1.bias"] = (cfg.mlp, h), (cfg.mlp,)
+        keys[f"{p}.mlp.fc2.weight"], keys[f"{p}.mlp.fc2.bias"] = (h, cfg.mlp), (h,)
+    return keys
+
+
+def load_safety_checker(model, sd: Dict[str, torch.Tensor]) -> int:
+    """Load a StableDiffusionSafetyChecker state dict into a
+    ClipSafetyChecker, strictly in both directions: a missing key, an
+    unexpected key or a shape mismatch raises ValueError naming the keys
+    (only a position_ids buffer is ignored, as older transformers versions
+    serialise one). Sets model.weights = "loaded"."""
+    sd = {k: v for k, v in sd.items() if not k.endswith("position_ids")}
+    want = safety_checker_key_map(model.cfg)
+    missing = sorted(set(want) - set(sd))
+    extra = sorted(set(sd) - set(want))
+    if missing or extra:
+        raise ValueError(
+            f"safety checker checkpoint does not match: missing {missing}, "
+            f"unexpected {extra}")
+    bad = [f"{k}: {tuple(sd[k].shape)} vs {want[k]}" for k in sorted(want)
+           if tuple(sd[k].shape) != want[k]]
+    if bad:
+        raise ValueError(f"safety checker shape mismatch: {bad}")
+    own = dict(model.state_dict())
+    with torch.no_grad():
+        for k in want:
+            own[k].copy_(sd[k].to(own[k].dtype))
+    from ..ops import drop_weight_caches
+
+    drop_weight_caches(model)
+    model.weights = "loaded"
+    return len(want)
+
+
+def find_safety_checker_file(model_dir=None):
+    """<model_dir>/safety_checker/model.safetensors, else the HF-cache
+    snapshot of CompVis/stable-diffusion-safety-checker, else None."""
+    import glob
+
+    cands = []
+    if model_dir:
+        cands.append(os.path.join(model_dir, "safety_checker", "model.safetensors"))
+    hub = os.environ.get("HF_HUB_CACHE", os.path.expanduser("~/.cache/huggingface/hub"))
+    cands += sorted(glob.glob(os.path.join(
+        hub, "models--" + SAFETY_CHECKER_REPO.replace("/", "--"), "snapshots",
+        "*", "model.safetensors")))
+    return next((p for p in cands if os.path.exists(p)), None)
+
+
+def load_safety_checker_if_present(checker, model_dir=None) -> bool:
+    """Fill a ClipSafetyChecker from the first checkpoint
+    find_safety_checker_file offers; False (random init stays) when there
+    is none or it does not match."""
+    import logging
+
+    from safetensors.torch import load_file
+
+    from .safety_clip import ClipSafetyChecker
+
+    if not isinstance(checker, ClipSafetyChecker) or checker.weights == "loaded":
+        return False
+    p = find_safety_checker_file(model_dir)
+    if p is None:
+        return False
+    try:
+        load_safety_checker(checker, load_file(p))
+    except ValueError as e:
+        logging.getLogger(__name__).warning(
+            "safety checker checkpoint %s skipped: %s", p, e)
+        return False
+    return True
+
+
 def load_model_dir(engine, model_dir: str) -> bool:
     """Load UNet (+ TAESD enc+dec) safetensors from a local diffusers-style
     directory; returns False when nothing was found (random init stays).
@@ -404,4 +511,8 @@ def load_model_dir(engine, model_dir: str) -> bool:
                     break
         if hasattr(te, "load_tokenizer_dir") and te.load_tokenizer_dir(model_dir):
             log.info("BPE tokenizer loaded from %s", model_dir)
+    # CLIP safety checker (reference lib/wrapper.py:930-942)
+    if load_safety_checker_if_present(getattr(engine, "safety_checker", None),
+                                      model_dir):
+        found = True
     return found

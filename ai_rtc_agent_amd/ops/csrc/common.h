@@ -45,6 +45,24 @@ __device__ __forceinline__ float apply_act(float v, int act) {
   return v;
 }
 
+// the decoder's f16 image in [-1, 1] -> the u8 level the viewer gets
+// (postprocess_u8, and clip_patches in front of the safety checker)
+__device__ __forceinline__ uint8_t post_u8(f16 x) {
+  const float f = ((float)x + 1.0f) * 127.5f;
+  return (uint8_t)min(255.0f, max(0.0f, nearbyintf(f)));
+}
+
+// tap window [start, end) and centre c of output pixel o of a separable
+// antialiased resize: scale = n_in / n_out, sup = the filter's support at
+// that scale (fit_resize_u8: max(scale, 1); clip_patches: twice that)
+__device__ __forceinline__ void fit_taps(int o, double scale, double sup,
+                                         int n_in, int& start, int& end,
+                                         double& c) {
+  c = (o + 0.5) * scale;
+  start = max((int)(c - sup + 0.5), 0);
+  end = min((int)(c + sup + 0.5), n_in);
+}
+
 // butterfly reduce over all 64 lanes of a wave (defined below, after the
 // DPP helpers: the first 4 steps run on the VALU pipe, only the two
 // cross-row steps pay the ds_bpermute cost)

@@ -46,13 +46,9 @@ extern "C" void airtc_preprocess_u8(const uint8_t* in, uint16_t* out, long n,
 }
 
 // ---------------------------------------------------------------------------
-// f16 in [-1,1] -> u8 with round+clamp (reference lib/pipeline.py:74)
+// f16 in [-1,1] -> u8 with round+clamp (reference lib/pipeline.py:74);
+// post_u8 is in common.h
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint8_t post_u8(f16 x) {
-  const float f = ((float)x + 1.0f) * 127.5f;
-  return (uint8_t)min(255.0f, max(0.0f, nearbyintf(f)));
-}
-
 // n any: the last n % 8 elements go one by one, as in preprocess_u8_kernel
 __global__ void postprocess_u8_kernel(const f16* __restrict__ in,
                                       uint8_t* __restrict__ out, long n8,
@@ -433,13 +429,7 @@ extern "C" void airtc_rcfg_apply(int mode, const uint16_t* eps,
 #define FIT_COLS (FIT_TW * 3)
 #define FIT_ROWS 32
 
-__device__ __forceinline__ void fit_taps(int o, double scale, double sup,
-                                         int n_in, int& start, int& end,
-                                         double& c) {
-  c = (o + 0.5) * scale;
-  start = max((int)(c - sup + 0.5), 0);
-  end = min((int)(c + sup + 0.5), n_in);
-}
+// fit_taps (the tap window of an output pixel) is in common.h
 
 __device__ __forceinline__ float fit_weight(float d, float inv_sup) {
   return fmaxf(0.0f, 1.0f - fabsf(d * inv_sup));

@@ -674,6 +674,123 @@ torch::Tensor canny_hint(torch::Tensor frames, torch::Tensor thr,
   return out;
 }
 
+// --- CLIP safety checker (safety.hip) ----------------------------------
+torch::Tensor clip_patches(torch::Tensor img, torch::Tensor lut, int64_t size,
+                           int64_t patch, int64_t nh, int64_t nw, int64_t top,
+                           int64_t left, torch::Tensor out) {
+  CHECK_IN(img);
+  TORCH_CHECK(img.dtype() == torch::kHalf, "clip_patches: img must be float16");
+  TORCH_CHECK(img.dim() == 4 && img.size(3) == 3,
+              "clip_patches: img must be (B, H, W, 3)");
+  const int64_t B = img.size(0), H = img.size(1), W = img.size(2);
+  TORCH_CHECK(B >= 1 && B <= kGridYZ, "clip_patches: B must be in [1, ",
+              kGridYZ, "], got ", B);
+  TORCH_CHECK(H >= 8 && W >= 8, "clip_patches: H and W must be >= 8, got ", H,
+              "x", W);
+  TORCH_CHECK(H * W * 3 <= kIntMax, "clip_patches: frame too large");
+  TORCH_CHECK(patch >= 1 && size >= patch && size % patch == 0 &&
+                  size * 3 <= kIntMax / 4,
+              "clip_patches: size must be a multiple of patch, got ", size,
+              " and ", patch);
+  TORCH_CHECK(nh <= kIntMax && nw <= kIntMax && top >= 0 && left >= 0 &&
+                  top + size <= nh && left + size <= nw,
+              "clip_patches: the ", size, "x", size, " window at (", top, ", ",
+              left, ") is not inside the resized ", nh, "x", nw);
+  check_operand(lut, img, torch::kHalf, 3 * 256, "clip_patches: lut");
+  const int64_t grid = size / patch;
+  check_operand(out, img, torch::kHalf, B * size * size * 3,
+                "clip_patches: out");
+  TORCH_CHECK(out.dim() == 3 && out.size(0) == B &&
+                  out.size(1) == grid * grid &&
+                  out.size(2) == 3 * patch * patch,
+              "clip_patches: out must be (B, ", grid * grid, ", ",
+              3 * patch * patch, ")");
+  airtc_clip_patches(h_ptr(img), h_ptr_mut(out), h_ptr(lut), (int)B, (int)H,
+                     (int)W, (int)size, (int)patch, (int)nh, (int)nw, (int)top,
+                     (int)left, cur_stream());
+  return out;
+}
+
+torch::Tensor quick_gelu(torch::Tensor x) {
+  CHECK_IN(x);
+  TORCH_CHECK(x.dtype() == torch::kHalf, "quick_gelu: x must be float16");
+  TORCH_CHECK(x.numel() % 8 == 0, "quick_gelu: the kernel handles 8 elements "
+              "per lane, numel must be a multiple of 8, got ", x.numel());
+  auto out = torch::empty_like(x);
+  if (x.numel() == 0) return out;
+  airtc_quick_gelu_f16(h_ptr(x), h_ptr_mut(out), x.numel(), cur_stream());
+  return out;
+}
+
+std::vector<torch::Tensor> safety_head(
+    torch::Tensor cls, torch::Tensor ln_g, torch::Tensor ln_b,
+    torch::Tensor proj_w, torch::Tensor concept, torch::Tensor concept_w,
+    torch::Tensor special, torch::Tensor special_w, torch::Tensor adjust,
+    torch::Tensor counters, double eps) {
+  // cls: (B, hidden) f16 rows with unit element stride; the row stride is
+  // free, so the tower's x[:, 0] runs zero-copy
+  TORCH_CHECK(cls.is_cuda() && cls.dim() == 2 && cls.dtype() == torch::kHalf,
+              "safety_head: cls must be a (B, hidden) float16 GPU tensor");
+  const int64_t B = cls.size(0), hidden = cls.size(1);
+  TORCH_CHECK(B >= 1 && B <= kIntMax, "safety_head: empty batch");
+  TORCH_CHECK(hidden > 0 && hidden % 8 == 0,
+              "safety_head: the kernel reads 8 channels per lane, hidden = ",
+              hidden);
+  TORCH_CHECK(cls.stride(1) == 1 && cls.stride(0) % 8 == 0 &&
+                  aligned16(cls.data_ptr()),
+              "safety_head: cls rows must be dense and start on 16-byte "
+              "boundaries");
+  check_operand(ln_g, cls, torch::kFloat, hidden, "safety_head: ln_g");
+  check_operand(ln_b, cls, torch::kFloat, hidden, "safety_head: ln_b");
+  check_operand(proj_w, cls, torch::kHalf, "safety_head: proj_w");
+  TORCH_CHECK(proj_w.dim() == 2 && proj_w.size(1) == hidden &&
+                  proj_w.size(0) >= 1,
+              "safety_head: proj_w must be (proj, hidden)");
+  TORCH_CHECK(aligned16(proj_w.data_ptr()),
+              "safety_head: proj_w must start on a 16-byte boundary");
+  const int64_t proj = proj_w.size(0);
+  check_operand(concept, cls, torch::kFloat, "safety_head: concept");
+  check_operand(special, cls, torch::kFloat, "safety_head: special");
+  TORCH_CHECK(concept.dim() == 2 && concept.size(1) == proj &&
+                  concept.size(0) >= 1 && special.dim() == 2 &&
+                  special.size(1) == proj && special.size(0) >= 1,
+              "safety_head: concept and special must be (n >= 1, proj)");
+  const int64_t nc = concept.size(0), ns = special.size(0);
+  check_operand(concept_w, cls, torch::kFloat, nc, "safety_head: concept_w");
+  check_operand(special_w, cls, torch::kFloat, ns, "safety_head: special_w");
+  check_operand(adjust, cls, torch::kFloat, B, "safety_head: adjust");
+  check_operand(counters, cls, torch::kInt, B, "safety_head: counters");
+  TORCH_CHECK(hidden + proj + ns + nc <= 15000,
+              "safety_head: hidden + proj + table rows must fit 64 KB of LDS");
+  auto flags = torch::empty({B}, cls.options().dtype(torch::kInt));
+  auto scores = torch::empty({B, ns + nc}, cls.options().dtype(torch::kFloat));
+  airtc_safety_head(h_ptr(cls), cls.stride(0), ln_g.data_ptr<float>(),
+                    ln_b.data_ptr<float>(), h_ptr(proj_w),
+                    special.data_ptr<float>(), special_w.data_ptr<float>(),
+                    concept.data_ptr<float>(), concept_w.data_ptr<float>(),
+                    adjust.data_ptr<float>(), counters.data_ptr<int>(),
+                    flags.data_ptr<int>(), scores.data_ptr<float>(), (int)B,
+                    (int)hidden, (int)proj, (int)ns, (int)nc, (float)eps,
+                    cur_stream());
+  return {flags, scores};
+}
+
+torch::Tensor blank_flagged_(torch::Tensor img, torch::Tensor flags) {
+  CHECK_IN(img);
+  TORCH_CHECK(img.dtype() == torch::kHalf,
+              "blank_flagged_: img must be float16");
+  TORCH_CHECK(img.dim() >= 1 && img.size(0) >= 1 && img.size(0) <= kGridYZ,
+              "blank_flagged_: img must hold 1..", kGridYZ, " frames");
+  const int64_t B = img.size(0);
+  check_operand(flags, img, torch::kInt, B, "blank_flagged_: flags");
+  const int64_t per = img.numel() / B;
+  if (per == 0) return img;
+  const int vec = per % 8 == 0 && aligned16(img.data_ptr()) ? 1 : 0;
+  airtc_blank_flagged(h_ptr_mut(img), flags.data_ptr<int>(), (int)B, per, vec,
+                      cur_stream());
+  return img;
+}
+
 // --- software H.264 baseline-intra codec (h264sw.cpp) -----------------
 extern "C" {
 void* airtc_h264enc_create(int w, int h);
@@ -1082,6 +1199,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "i32 read on the device, hysteresis bounded to `reach` steps",
         pybind11::arg("frames"), pybind11::arg("thr"), pybind11::arg("reach"),
         pybind11::arg("out"));
+  m.def("clip_patches", &clip_patches,
+        "decoder image -> CLIP patch rows (resize, crop, normalise), one "
+        "launch, into `out`");
+  m.def("quick_gelu", &quick_gelu);
+  m.def("safety_head", &safety_head,
+        "class token -> (flags i32, scores f32); counters += flags");
+  m.def("blank_flagged_", &blank_flagged_,
+        "flagged frames -> -1, in place");
   m.def("conv2d_fp8", &conv2d_fp8,
         "fp8 e4m3 implicit-GEMM conv2d on the MX-scaled MFMA (NHWC)",
         pybind11::arg("x"), pybind11::arg("w_fp8"), pybind11::arg("dq"),

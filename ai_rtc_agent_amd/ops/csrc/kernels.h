@@ -53,6 +53,39 @@ void airtc_i420_to_rgb_u8(const uint8_t* in, uint8_t* out, int B, int H,
 int airtc_canny_hint(const uint8_t* in, const int* thr, void* out,
                      int out_f32, int B, int H, int W, int reach,
                      hipStream_t s);
+// CLIP safety checker (safety.hip) -------------------------------------------
+// (B,H,W,3) f16 decoder image -> (B, (size/patch)^2, 3*patch^2) f16 patches
+// in (c, py, px) order: post_u8 per pixel, antialiased bicubic resize to
+// (nh, nw), round to u8, the size x size window at (top, left), then
+// lut[c*256 + v] (3x256 f16: (v/255 - mean_c)/std_c). Geometry is validated
+// by the caller (ext.cpp): size % patch == 0, top + size <= nh,
+// left + size <= nw, B <= 65535.
+void airtc_clip_patches(const uint16_t* img, uint16_t* out,
+                        const uint16_t* lut, int B, int H, int W, int size,
+                        int patch, int nh, int nw, int top, int left,
+                        hipStream_t s);
+// x * sigmoid(1.702 x), n % 8 == 0
+void airtc_quick_gelu_f16(const uint16_t* in, uint16_t* out, long n,
+                          hipStream_t s);
+// dynamic LDS the head kernel asks for; the caller keeps it under 64 KB
+int airtc_safety_head_lds_bytes(int hidden, int proj, int ns, int nc);
+// class token (B rows of `hidden` f16, cls_stride elements apart) ->
+// LayerNorm (f32 g, b) -> proj_w (proj, hidden) f16 GEMV -> cosines against
+// unit-norm f32 tables special (ns, proj) and concept (nc, proj) -> the
+// checker's decision with adjust[b]: flags (B,) i32, scores (B, ns + nc) f32
+// (special first), counters[b] += flag. hidden % 8 == 0; cls rows and proj_w
+// 16-byte aligned.
+void airtc_safety_head(const uint16_t* cls, long cls_stride, const float* ln_g,
+                       const float* ln_b, const uint16_t* proj_w,
+                       const float* special, const float* special_w,
+                       const float* concept, const float* concept_w,
+                       const float* adjust, int* counters, int* flags,
+                       float* scores, int B, int hidden, int proj, int ns,
+                       int nc, float eps, hipStream_t s);
+// frames b of img (B rows of `per` f16) with flags[b] != 0 become -1, in
+// place. vec != 0: per % 8 == 0 and img 16-byte aligned.
+void airtc_blank_flagged(uint16_t* img, const int* flags, int B, long per,
+                         int vec, hipStream_t s);
 // fused LCM scheduler math (one kernel each; coefficients are per-batch-row
 // f32 arrays of B entries, per_b = elements per batch row)
 void airtc_sched_add_noise(const uint16_t* x0, const uint16_t* noise,

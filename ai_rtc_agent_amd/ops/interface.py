@@ -1393,3 +1393,225 @@ def i420_to_rgb_u8(x: torch.Tensor, H: int | None = None,
         if ob is not None:
             ob.copy_(res)
     return _finish(res, out, squeeze)
+
+
+# ---------------------------------------------------------------------------
+# CLIP safety checker (ops/csrc/safety.hip; models/safety_clip.py)
+# ---------------------------------------------------------------------------
+# The preprocessing, stated once. It is what CLIPImageProcessor does to the
+# u8 frame the viewer would get, and the torch forms below are its
+# definition (the HIP kernel computes the same thing in one launch):
+#   1. every input pixel goes to the u8 level postprocess_to_u8 writes:
+#      clamp(round_half_even((x + 1) * 127.5), 0, 255), in f32
+#   2. resize so that the shorter side is `size`, the longer one
+#      int(size * long / short): separable (horizontal, then vertical)
+#      antialiased bicubic, Keys a = -0.5. Per axis scale = n_in / n_out,
+#      fs = max(scale, 1), centre c = (o + 0.5) * scale, taps
+#      [max(int(c - 2 fs + 0.5), 0), min(int(c + 2 fs + 0.5), n_in)), weight
+#      k((j - c + 0.5) / fs) normalised to sum 1: the filter of PIL BICUBIC
+#      and of F.interpolate(mode="bicubic", antialias=True,
+#      align_corners=False). Nothing is rounded between the two passes (PIL
+#      rounds to 8 bits there, so it differs by a few levels)
+#   3. round half even, clamp to [0, 255]
+#   4. centre crop size x size: top = (nh - size) // 2, left likewise
+#   5. (v / 255 - mean_c) / std_c, evaluated in f64 per level and channel
+#      and rounded once to f16 (a 3 x 256 table)
+# and the result is laid out as the patch-embedding GEMM's A operand:
+# (B, (size/patch)^2, 3 * patch^2), elements in (c, py, px) order.
+
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+def clip_geometry(H: int, W: int, size: int) -> tuple:
+    """(nh, nw, top, left): the resized extent and the crop window in it."""
+    short, long_ = (W, H) if W <= H else (H, W)
+    new_long = int(size * long_ / short)
+    nh, nw = (new_long, size) if W <= H else (size, new_long)
+    return nh, nw, (nh - size) // 2, (nw - size) // 2
+
+
+def _keys_cubic(x: torch.Tensor) -> torch.Tensor:
+    x = x.abs()
+    near = (1.5 * x - 2.5) * x * x + 1.0
+    far = ((-0.5 * x + 2.5) * x - 4.0) * x + 2.0
+    return torch.where(x < 1.0, near, torch.where(x < 2.0, far, torch.zeros_like(x)))
+
+
+def _aa_cubic_weights(n_in: int, n_out: int, first: int, count: int) -> torch.Tensor:
+    """(count, n_in) f64: row i holds the normalised taps of output pixel
+    first + i of an n_in -> n_out antialiased bicubic resize."""
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    c = (torch.arange(first, first + count, dtype=torch.float64) + 0.5) * scale
+    start = (c - 2.0 * fs + 0.5).trunc().clamp_min(0)
+    end = (c + 2.0 * fs + 0.5).trunc().clamp_max(n_in)
+    j = torch.arange(n_in, dtype=torch.float64)
+    w = _keys_cubic((j[None] - c[:, None] + 0.5) / fs)
+    w = w * ((j[None] >= start[:, None]) & (j[None] < end[:, None]))
+    return w / w.sum(dim=1, keepdim=True)
+
+
+def clip_resize_reference(img: torch.Tensor, size: int = 224,
+                          dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Steps 1, 2 and 4 above in `dtype` arithmetic: (B,H,W,3) in [-1,1] ->
+    (B,size,size,3) levels BEFORE the rounding of step 3 (float64 is what
+    the GPU tests hold the kernel against)."""
+    _, H, W, _ = img.shape
+    nh, nw, top, left = clip_geometry(H, W, size)
+    u8 = ((img.float() + 1.0) * 127.5).round().clamp(0, 255)
+    wx = _aa_cubic_weights(W, nw, left, size).to(device=img.device, dtype=dtype)
+    wy = _aa_cubic_weights(H, nh, top, size).to(device=img.device, dtype=dtype)
+    t = torch.einsum("ow,bhwc->bhoc", wx, u8.to(dtype))
+    return torch.einsum("ph,bhoc->bpoc", wy, t)
+
+
+_CLIP_LUT: dict = {}
+
+
+def clip_lut(device) -> torch.Tensor:
+    """(3, 256) f16: step 5 for every channel and level, cached per device."""
+    device = torch.device(device)
+    lut = _CLIP_LUT.get(device)
+    if lut is None:
+        v = torch.arange(256, dtype=torch.float64)[None] / 255.0
+        mean = torch.tensor(CLIP_MEAN, dtype=torch.float64)[:, None]
+        std = torch.tensor(CLIP_STD, dtype=torch.float64)[:, None]
+        lut = ((v - mean) / std).to(torch.float16).contiguous().to(device)
+        _CLIP_LUT[device] = lut
+    return lut
+
+
+def clip_levels_to_patches(levels: torch.Tensor, patch: int) -> torch.Tensor:
+    """(B,size,size,3) integer levels -> (B, (size/patch)^2, 3*patch^2) f16."""
+    B, size = levels.shape[0], levels.shape[1]
+    g = size // patch
+    lut = clip_lut(levels.device)
+    vals = lut[torch.arange(3, device=levels.device), levels.long()]
+    vals = vals.reshape(B, g, patch, g, patch, 3).permute(0, 1, 3, 5, 2, 4)
+    return vals.reshape(B, g * g, 3 * patch * patch).contiguous()
+
+
+def clip_patches(img: torch.Tensor, size: int = 224, patch: int = 14,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """Decoder image (B,H,W,3) f16/f32 in [-1,1] -> the CLIP tower's patch
+    rows (B, (size/patch)^2, 3*patch^2) f16, by the preprocessing defined
+    above. Any H, W >= 8; size a multiple of patch.
+
+    GPU f16: ONE launch of clip_patches (ops/csrc/safety.hip) on the current
+    stream; the only allocation is `out` when it is not given. Everything
+    else (CPU, f32, AIRTC_FORCE_EAGER=1) takes the torch form."""
+    if img.dim() != 4 or img.shape[-1] != 3 or not img.dtype.is_floating_point:
+        raise ValueError(
+            f"clip_patches needs a float image (B,H,W,3), got {img.dtype} "
+            f"{tuple(img.shape)}")
+    B, H, W, _ = img.shape
+    if B < 1 or H < 8 or W < 8:
+        raise ValueError(f"clip_patches needs B >= 1 and H, W >= 8, got {tuple(img.shape)}")
+    if patch < 1 or size < patch or size % patch:
+        raise ValueError(f"size must be a multiple of patch, got {size} and {patch}")
+    g = size // patch
+    shape = (B, g * g, 3 * patch * patch)
+    if out is not None and (
+            out.dtype != torch.float16 or tuple(out.shape) != shape
+            or out.device != img.device or not out.is_contiguous()):
+        raise ValueError(
+            f"out must be a contiguous float16 {shape} tensor on {img.device}")
+    if _use_hip(img):
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float16, device=img.device)
+        nh, nw, top, left = clip_geometry(H, W, size)
+        return _require_ext().clip_patches(
+            img.contiguous(), clip_lut(img.device), size, patch, nh, nw, top,
+            left, out)
+    levels = clip_resize_reference(img, size).round().clamp(0, 255)
+    res = clip_levels_to_patches(levels, patch)
+    if out is not None:
+        out.copy_(res)
+        return out
+    return res
+
+
+def quick_gelu(x: torch.Tensor) -> torch.Tensor:
+    """x * sigmoid(1.702 x), CLIP's activation. GPU f16: vec8 kernel, f32
+    math; shapes the vector path cannot read take the torch form."""
+    if _use_hip(x) and x.numel() % 8 == 0:
+        return _require_ext().quick_gelu(x.contiguous())
+    xf = x.float()
+    return (xf * torch.sigmoid(1.702 * xf)).to(x.dtype)
+
+
+# The decision law of the reference StableDiffusionSafetyChecker, in order
+# (cos against unit-norm rows; adj is its `adjustment`, positive = stricter):
+#   special_j = cos_j - special_w_j + adj
+#   care      = 0.01 if any(special_j > 0) else 0
+#   concept_i = cos_i - concept_w_i + adj + care
+#   flagged   = any(concept_i > 0)
+
+def _unit_rows(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    t = t.detach().to(dtype)
+    return (t / t.norm(dim=-1, keepdim=True)).contiguous()
+
+
+def safety_head_reference(cls, ln_g, ln_b, proj_w, concept, concept_w,
+                          special, special_w, adjust, eps: float = 1e-5,
+                          dtype: torch.dtype = torch.float32):
+    """LayerNorm -> projection -> cosines -> the law above, in `dtype`
+    arithmetic. Returns (flags int32 (B,), scores `dtype` (B, ns + nc),
+    special first)."""
+    y = F.layer_norm(cls.to(dtype), (cls.shape[-1],), ln_g.to(dtype),
+                     ln_b.to(dtype), eps)
+    e = y @ proj_w.to(dtype).t()
+    e = e / e.norm(dim=-1, keepdim=True)
+    adj = adjust.to(dtype)[:, None]
+    sp = e @ _unit_rows(special, dtype).t() - special_w.to(dtype)[None] + adj
+    care = (sp > 0).any(dim=1, keepdim=True).to(dtype) * 0.01
+    co = e @ _unit_rows(concept, dtype).t() - concept_w.to(dtype)[None] + adj + care
+    flags = (co > 0).any(dim=1).to(torch.int32)
+    return flags, torch.cat([sp, co], dim=1)
+
+
+def safety_head(cls: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor,
+                proj_w: torch.Tensor, concept: torch.Tensor,
+                concept_w: torch.Tensor, special: torch.Tensor,
+                special_w: torch.Tensor, adjust: torch.Tensor,
+                counters: torch.Tensor, eps: float = 1e-5):
+    """Everything after the tower, per frame: cls (B, hidden) class tokens
+    -> (flags int32 (B,), scores f32 (B, n_special + n_concept)) by
+    safety_head_reference, and counters[b] += flags[b] in place. adjust is
+    (B,) f32 and counters (B,) int32, both read on the device: a captured
+    graph follows in-place writes to them.
+
+    GPU f16: ONE launch, one workgroup per frame (ops/csrc/safety.hip); f16
+    cls and proj_w, f32 accumulation, nothing rounded to f16 on the way. The
+    embedding tables are normalised once and cached on their tensors
+    (weight_cache). Needs hidden % 8 == 0."""
+    if adjust.dtype != torch.float32 or counters.dtype != torch.int32:
+        raise TypeError("safety_head: adjust must be float32 and counters int32")
+    if _use_hip(cls):
+        ext = _require_ext()
+        unit = lambda t: weight_cache(  # noqa: E731
+            t, "_airtc_unit32", lambda: _unit_rows(t, torch.float32))
+        flags, scores = ext.safety_head(
+            cls, _f32(ln_g, "_airtc_g32"), _f32(ln_b, "_airtc_b32"), proj_w,
+            unit(concept), _f32(concept_w, "_airtc_w32"), unit(special),
+            _f32(special_w, "_airtc_w32"), adjust, counters, eps)
+        return flags, scores
+    flags, scores = safety_head_reference(
+        cls, ln_g, ln_b, proj_w, concept, concept_w, special, special_w,
+        adjust, eps)
+    counters += flags
+    return flags, scores.float()
+
+
+def blank_flagged_(img: torch.Tensor, flags: torch.Tensor) -> torch.Tensor:
+    """In place: frames b of img (B, ...) with flags[b] != 0 become -1
+    (black) everywhere; the others are not written. No host sync."""
+    if flags.dtype != torch.int32 or flags.numel() != img.shape[0]:
+        raise ValueError("flags must be int32, one per frame")
+    if _use_hip(img):
+        if not img.is_contiguous():
+            raise ValueError("img must be contiguous (it is written in place)")
+        return _require_ext().blank_flagged_(img, flags)
+    return img.masked_fill_(
+        (flags != 0).view(-1, *([1] * (img.dim() - 1))), -1.0)
