@@ -370,6 +370,8 @@ async def on_startup(app: web.Application) -> None:
         if app.get("safety_checker") or os.environ.get("AIRTC_SAFETY_CHECKER"):
             # naming a checker (flag or environment) switches the gate on
             cfg.use_safety_checker = True
+        if app.get("full_vae"):
+            cfg.use_tiny_vae = False
         cfg.__post_init__()  # validate what was set after construction
         st["pool"] = PipelinePool.create(
             model_id=app["model_id"], n_gpus=app["n_gpus"], cfg=cfg,
@@ -419,6 +421,7 @@ def create_app(
     canny_reach: Optional[int] = None,
     safety_checker: Optional[str] = None,
     safety_adjustment: Optional[float] = None,
+    full_vae: bool = False,
 ) -> web.Application:
     app = web.Application(middlewares=[cors_middleware])
     app["model_id"] = model_id
@@ -445,6 +448,8 @@ def create_app(
     # the runtime config: a publisher must not relax its own gate
     app["safety_checker"] = safety_checker
     app["safety_adjustment"] = safety_adjustment
+    # False: EngineConfig default (AIRTC_TINY_VAE); True: the full AutoencoderKL
+    app["full_vae"] = full_vae
     app["state"] = {
         "pcs": set(),
         "source_track": None,
@@ -469,7 +474,7 @@ def create_app(
     return app
 
 
-def main() -> None:
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="MI355X real-time video-diffusion agent")
     parser.add_argument("--model-id", default="lykon/dreamshaper-8")
     parser.add_argument("--port", type=int, default=8888)
@@ -544,6 +549,12 @@ def main() -> None:
                              "captured decode graph; tiny = the small conv "
                              "classifier (default: $AIRTC_SAFETY_CHECKER, "
                              "else no checker)")
+    parser.add_argument("--full-vae", action="store_true",
+                        help="decode and encode with the checkpoint's full "
+                             "AutoencoderKL instead of TAESD: sharper frames "
+                             "at about a third of the frame rate; sd15 / sd21 "
+                             "only (default: $AIRTC_TINY_VAE=0 asks for it "
+                             "too)")
     parser.add_argument("--safety-adjustment", type=float, default=None,
                         help="added to every clip checker score, positive is "
                              "stricter; operator-only, not reachable from "
@@ -559,7 +570,11 @@ def main() -> None:
                              "(one per GPU, own media sockets) behind a "
                              "signalling front-end (SURVEY.md §5.8); 0 = "
                              "single-process mode")
-    args = parser.parse_args()
+    return parser
+
+
+def main() -> None:
+    args = build_parser().parse_args()
 
     logging.basicConfig(level=getattr(logging, args.log_level.upper(), logging.INFO))
     if args.yuv:
@@ -597,6 +612,8 @@ def main() -> None:
                           ("safety_adjustment", "AIRTC_SAFETY_ADJUSTMENT")):
             if getattr(args, flag) is not None:
                 os.environ[env] = str(getattr(args, flag))
+        if args.full_vae:
+            os.environ["AIRTC_TINY_VAE"] = "0"
         fe = WorkerFrontend(args.workers, model_id=args.model_id,
                             family=args.family, resolution=args.resolution,
                             pin_gpu=torch.cuda.is_available(),
@@ -618,7 +635,8 @@ def main() -> None:
                      canny_low=args.canny_low, canny_high=args.canny_high,
                      canny_reach=args.canny_reach,
                      safety_checker=args.safety_checker,
-                     safety_adjustment=args.safety_adjustment)
+                     safety_adjustment=args.safety_adjustment,
+                     full_vae=args.full_vae)
     web.run_app(app, host=args.host, port=args.port)
 
 

@@ -79,6 +79,11 @@ def _env_float(name: str, default: float) -> float:
 # AIRTC_SAFETY_ADJUSTMENT (float)     -> EngineConfig.safety_adjustment: added
 #                                        to every clip score, positive is
 #                                        stricter
+# AIRTC_TINY_VAE (0|1)                -> EngineConfig.use_tiny_vae: 1 (default)
+#                                        = TAESD; 0 = the checkpoint's full
+#                                        AutoencoderKL (models/vae_kl.py):
+#                                        sharper decode at about a third of the
+#                                        frame rate. sd15 / sd21 only
 
 
 def engines_cache_dir() -> str:
@@ -164,7 +169,9 @@ class EngineConfig:
     frame_buffer_size: int = 1
     use_denoising_batch: bool = True
     use_lcm_lora: bool = True
-    use_tiny_vae: bool = True
+    # False: the checkpoint's own AutoencoderKL (models/vae_kl.py) instead of
+    # TAESD, as the reference's use_tiny_vae=False. Not for sdxl (below).
+    use_tiny_vae: bool = field(default_factory=lambda: _env_bool("AIRTC_TINY_VAE", True))
     do_add_noise: bool = True
     dtype: str = "float16"
     seed: int = 2
@@ -255,6 +262,12 @@ class EngineConfig:
     canny_reach: int = field(default_factory=lambda: _env_int("AIRTC_CANNY_REACH", 16))
 
     def __post_init__(self) -> None:
+        if not self.use_tiny_vae and self.model_family in ("sdxl", "tiny_xl"):
+            raise ValueError(
+                f"use_tiny_vae=False is not available for model_family="
+                f"{self.model_family!r}: SDXL's AutoencoderKL overflows "
+                f"float16, and its float32-upcast route is not built; keep "
+                f"the tiny VAE for sdxl")
         if self.safety_checker not in SAFETY_CHECKERS:
             raise ValueError(
                 f"safety_checker must be one of {SAFETY_CHECKERS}, "

@@ -84,7 +84,18 @@ class StreamDiffusionEngine:
 
         ucfg = _unet_config_for(cfg.model_family)
         self.unet = unet if unet is not None else UNet2DCondition(ucfg)
-        self.vae = vae if vae is not None else TinyVAE()
+        if vae is not None:
+            self.vae = vae
+        elif cfg.use_tiny_vae:
+            self.vae = TinyVAE()
+        else:
+            # the checkpoint's full AutoencoderKL; the tiny test family gets
+            # a two-block stand-in of the same architecture
+            from ..models.vae_kl import (AutoencoderKLVAE, KLConfig,
+                                         TINY_KL_CONFIG)
+            self.vae = AutoencoderKLVAE(
+                TINY_KL_CONFIG if cfg.model_family == "tiny" else KLConfig(),
+                device=self.device)
         # family conventions: SD1.5 = CLIP ViT-L/14 (quick-gelu, last
         # layer); SD2.x = OpenCLIP ViT-H (gelu, PENULTIMATE layer, 23
         # blocks); sdxl = the DUAL encoder (ViT-L + OpenCLIP bigG, both

@@ -10,7 +10,8 @@ engines--<model>/
     plan.json            engine config + kernel-plan metadata (shapes,
                          conv path/split-K decisions, attention dims)
     unet.safetensors     fused (LoRA-applied) UNet weights, fp16
-    vae.safetensors      TinyVAE weights, fp16
+    vae.safetensors      TinyVAE weights, fp16 (AutoencoderKL weights in
+                         engines--<model>--full-vae/, use_tiny_vae=False)
     text_encoder.safetensors
 
 Loading a plan skips model init + LoRA fusion; the hipGraph itself is
@@ -29,9 +30,14 @@ import torch
 from ..config import EngineConfig, engines_cache_dir
 
 
-def plan_dir(model_id: str, cache_root: Optional[str] = None) -> str:
-    # naming contract: engines--<model-id with '/' -> '--'>
+def plan_dir(model_id: str, cache_root: Optional[str] = None,
+             tiny_vae: bool = True) -> str:
+    # naming contract: engines--<model-id with '/' -> '--'>; a plan built
+    # with the checkpoint's full AutoencoderKL (use_tiny_vae=False) holds
+    # other VAE weights under the same file name, so it gets its own key
     name = "engines--" + model_id.replace("/", "--")
+    if not tiny_vae:
+        name += "--full-vae"
     return os.path.join(cache_root or engines_cache_dir(), name)
 
 
@@ -43,7 +49,7 @@ def _cfg_dict(cfg: EngineConfig) -> dict:
 def save_plan(engine, cache_root: Optional[str] = None) -> str:
     from safetensors.torch import save_file
 
-    out = plan_dir(engine.cfg.model_id, cache_root)
+    out = plan_dir(engine.cfg.model_id, cache_root, engine.cfg.use_tiny_vae)
     os.makedirs(out, exist_ok=True)
 
     def dump(module: torch.nn.Module, name: str) -> None:
@@ -71,7 +77,7 @@ def load_plan(cfg: EngineConfig, cache_root: Optional[str] = None):
     ladder, lib/wrapper.py:611-615)."""
     from safetensors.torch import load_file
 
-    d = plan_dir(cfg.model_id, cache_root)
+    d = plan_dir(cfg.model_id, cache_root, cfg.use_tiny_vae)
     if not os.path.exists(os.path.join(d, "plan.json")):
         return None
     from .engine import StreamDiffusionEngine
@@ -112,6 +118,8 @@ def kernel_plan_for(cfg: EngineConfig) -> dict:
         "latent": [lat, cfg.latent_width],
         "unet_batch": cfg.unet_batch,
         "attention_head_dims": "32/64/96/128/160 native; others zero-padded",
+        "vae": "taesd" if cfg.use_tiny_vae else
+               "autoencoder_kl (mid-block attention: one 512-wide head)",
         "conv_paths": {
             "large_spatial": "BM128xBN64 MFMA, split-K to >=480 workgroups",
             "small_spatial": "BM64xBN64 MFMA, split-K to >=512 workgroups",

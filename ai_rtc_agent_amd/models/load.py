@@ -433,6 +433,119 @@ def load_safety_checker_if_present(checker, model_dir=None) -> bool:
     return True
 
 
+# ---------------------------------------------------------------------------
+# AutoencoderKL (the vae/ folder of SD1.5 / SD2.1 / SD-Turbo snapshots) into
+# models/vae_kl.py. Explicit map: checkpoint layer -> module path; the
+# attention's to_q / to_k / to_v are packed into the module's one to_qkv.
+# Unvalidated against a published snapshot until a weights volume exists
+# (ROADMAP item 7); the synthetic round trip pins names and shapes.
+# ---------------------------------------------------------------------------
+_KL_ATTN_LEGACY = {"query": "to_q", "key": "to_k", "value": "to_v",
+                   "proj_attn": "to_out.0"}
+
+
+def autoencoder_kl_key_map(cfg) -> Tuple[Dict[str, str], Dict[str, str]]:
+    """(layers, attentions) of a diffusers AutoencoderKL for `cfg`:
+    layers maps a checkpoint layer prefix (it owns `.weight` and `.bias`) to
+    the AutoencoderKLVAE submodule path; attentions maps a checkpoint
+    attention prefix (group_norm, to_q, to_k, to_v, to_out.0 under it) to the
+    _Attention module path."""
+    layers: Dict[str, str] = {"quant_conv": "quant_conv",
+                              "post_quant_conv": "post_quant_conv"}
+    attns: Dict[str, str] = {}
+    nb = len(cfg.block_out_channels)
+    ch = cfg.block_out_channels
+
+    def resnet(ck: str, own: str, shortcut: bool):
+        for name in ("norm1", "conv1", "norm2", "conv2"):
+            layers[f"{ck}.{name}"] = f"{own}.{name}"
+        if shortcut:
+            layers[f"{ck}.conv_shortcut"] = f"{own}.conv_shortcut"
+
+    for side, blocks, per, sampler, own_sampler, widths in (
+            ("encoder", "down_blocks", cfg.layers_per_block, "downsamplers",
+             "downsample", ch),
+            ("decoder", "up_blocks", cfg.layers_per_block + 1, "upsamplers",
+             "upsample", tuple(reversed(ch)))):
+        for name in ("conv_in", "conv_norm_out", "conv_out"):
+            layers[f"{side}.{name}"] = f"{side}.{name}"
+        for i in range(nb):
+            cin = widths[max(i - 1, 0)]
+            for j in range(per):
+                resnet(f"{side}.{blocks}.{i}.resnets.{j}",
+                       f"{side}.{blocks}.{i}.resnets.{j}",
+                       j == 0 and cin != widths[i])
+            if i < nb - 1:
+                layers[f"{side}.{blocks}.{i}.{sampler}.0.conv"] = \
+                    f"{side}.{blocks}.{i}.{own_sampler}"
+        for j in (0, 1):
+            resnet(f"{side}.mid_block.resnets.{j}",
+                   f"{side}.mid_block.resnets.{j}", False)
+        attns[f"{side}.mid_block.attentions.0"] = f"{side}.mid_block.attention"
+    return layers, attns
+
+
+def load_autoencoder_kl(vae, sd: Dict[str, torch.Tensor]) -> int:
+    """Load a diffusers AutoencoderKL state dict into an AutoencoderKLVAE,
+    strictly in both directions: every checkpoint key is consumed and every
+    parameter filled, else ValueError naming the keys. The legacy attention
+    names (query, key, value, proj_attn) and their 1x1-conv-shaped (C,C,1,1)
+    weights are accepted. Returns the number of checkpoint tensors read."""
+    layers, attns = autoencoder_kl_key_map(vae.cfg)
+    sd = dict(sd)
+    for k in list(sd):  # legacy attention names -> current ones
+        for ap in attns:
+            if k.startswith(ap + "."):
+                head, _, leaf = k[len(ap) + 1:].rpartition(".")
+                if head in _KL_ATTN_LEGACY:
+                    sd[f"{ap}.{_KL_ATTN_LEGACY[head]}.{leaf}"] = sd.pop(k)
+    own = dict(vae.named_parameters())
+    plan = []        # (parameter name, tensor)
+    used, missing = set(), []
+
+    def take(key: str):
+        if key not in sd:
+            missing.append(key)
+            return None
+        used.add(key)
+        return sd[key]
+
+    def flat2(t):    # (C, C, 1, 1) conv-shaped linear weight -> (C, C)
+        return t.reshape(t.shape[0], t.shape[1]) if t is not None and t.dim() == 4 else t
+
+    for ck, path in layers.items():
+        for leaf in ("weight", "bias"):
+            plan.append((f"{path}.{leaf}", take(f"{ck}.{leaf}")))
+    for ck, path in attns.items():
+        for leaf in ("weight", "bias"):
+            plan.append((f"{path}.group_norm.{leaf}", take(f"{ck}.group_norm.{leaf}")))
+            parts = [take(f"{ck}.{n}.{leaf}") for n in ("to_q", "to_k", "to_v")]
+            if leaf == "weight":
+                parts = [flat2(t) for t in parts]
+            plan.append((f"{path}.to_qkv.{leaf}",
+                         None if any(t is None for t in parts)
+                         else torch.cat(parts, dim=0)))
+            out = take(f"{ck}.to_out.0.{leaf}")
+            plan.append((f"{path}.to_out.{leaf}", flat2(out) if leaf == "weight" else out))
+    extra = sorted(set(sd) - used)
+    unfilled = sorted(set(own) - {name for name, _ in plan})
+    if missing or extra or unfilled:
+        raise ValueError(
+            f"AutoencoderKL checkpoint does not match: missing {sorted(missing)}, "
+            f"unexpected {extra}, parameters left unfilled {unfilled}")
+    bad = [f"{name}: {tuple(t.shape)} vs {tuple(own[name].shape)}"
+           for name, t in plan if tuple(t.shape) != tuple(own[name].shape)]
+    if bad:
+        raise ValueError(f"AutoencoderKL shape mismatch: {bad}")
+    with torch.no_grad():
+        for name, t in plan:
+            own[name].copy_(t.to(own[name].dtype))
+    from ..ops import drop_weight_caches
+
+    drop_weight_caches(vae)
+    return len(used)
+
+
 def load_model_dir(engine, model_dir: str) -> bool:
     """Load UNet (+ TAESD enc+dec) safetensors from a local diffusers-style
     directory; returns False when nothing was found (random init stays).
@@ -441,7 +554,10 @@ def load_model_dir(engine, model_dir: str) -> bool:
     madebyollin/taesd: the diffusers AutoencoderTiny file sits at the
     snapshot TOP LEVEL; the raw split files are taesd_encoder/decoder;
     dreamshaper-8's vae/ subdir is a full AutoencoderKL that cannot populate
-    a TinyVAE — it is detected and skipped with a warning."""
+    a TinyVAE — it is detected and skipped with a warning, unless the engine
+    was built with use_tiny_vae=False: its AutoencoderKLVAE is then filled
+    from that file (load_autoencoder_kl, strict) and TAESD files are passed
+    over."""
     import logging
 
     from safetensors.torch import load_file
@@ -457,6 +573,9 @@ def load_model_dir(engine, model_dir: str) -> bool:
             else:
                 found = True
             break
+    from .vae_kl import AutoencoderKLVAE
+
+    kl_vae = isinstance(getattr(engine, "vae", None), AutoencoderKLVAE)
     n_enc = n_dec = 0
     for sub in (
         "taesd.safetensors",
@@ -467,6 +586,13 @@ def load_model_dir(engine, model_dir: str) -> bool:
         if not os.path.exists(p):
             continue
         sd = load_file(p)
+        if _is_autoencoder_kl(sd) and kl_vae:
+            # use_tiny_vae=False: the checkpoint's own VAE is the one wanted
+            n_enc = n_dec = load_autoencoder_kl(engine.vae, sd)
+            found = True
+            break
+        if kl_vae:
+            continue  # a TAESD file cannot fill an AutoencoderKL
         if _is_autoencoder_kl(sd):
             log.warning("%s is a full AutoencoderKL, not TAESD; skipping "
                         "(fetch madebyollin/taesd for the TinyVAE weights)", p)
@@ -476,19 +602,20 @@ def load_model_dir(engine, model_dir: str) -> bool:
             found = True
             break
     # raw split files (madebyollin/taesd also ships these)
-    if n_enc == 0:
+    if n_enc == 0 and not kl_vae:
         p = os.path.join(model_dir, "taesd_encoder.safetensors")
         if os.path.exists(p):
             n_enc = load_taesd_encoder(engine.vae.encoder, load_file(p), prefix="")
             found = found or n_enc > 0
-    if n_dec == 0:
+    if n_dec == 0 and not kl_vae:
         p = os.path.join(model_dir, "taesd_decoder.safetensors")
         if os.path.exists(p):
             n_dec = load_taesd_decoder(engine.vae.decoder, load_file(p), prefix="")
             found = found or n_dec > 0
     if found and n_enc == 0 and n_dec == 0:
-        log.warning("model dir %s: UNet loaded but no TAESD weights matched — "
-                    "VAE stays random-init", model_dir)
+        log.warning("model dir %s: UNet loaded but no %s weights matched — "
+                    "VAE stays random-init", model_dir,
+                    "AutoencoderKL" if kl_vae else "TAESD")
     # CLIP text encoder(s) + BPE tokenizer(s)
     # (reference lib/wrapper.py:468-473; sdxl adds text_encoder_2)
     te = getattr(engine, "text_encoder", None)

@@ -27,48 +27,10 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "lds_tr.h"  // tr_bfrag
 
 #define KVT 64  // kv tile
 #define QT 64   // q rows per workgroup
-
-typedef __attribute__((__vector_size__(2 * sizeof(unsigned)))) unsigned u32x2;
-typedef __attribute__((__vector_size__(4 * sizeof(_Float16)))) _Float16 f16x4;
-typedef const __attribute__((address_space(3))) f16* lds_cptr;
-
-__device__ __forceinline__ unsigned lds_addr(const f16* p) {
-  return (unsigned)(unsigned long long)(lds_cptr)p;
-}
-
-// B-fragment (8 keys x 16 cols) from a ROW-major [kv][pitch] f16 tile via two
-// hardware transpose reads. Per 16-lane group g (= keys kbase+8g..+7): lane
-// il supplies the address of its 4 contiguous f16 (row kbase+(il>>2),
-// col c0+(il&3)*4); the read hands lane il column c0+il over those rows.
-// Alignment: addresses are 8B-aligned (pitch even in f16) — required, a
-// misaligned tr read returns wrong data silently (guide G17).
-__device__ __forceinline__ f16x8 tr_bfrag(const f16* tile, int pitch,
-                                          int kbase, int c0, int lane) {
-  const int il = lane & 15;
-  const int g = lane >> 4;
-  const f16* p0 = tile + (kbase + g * 8 + (il >> 2)) * pitch + c0 + (il & 3) * 4;
-  const unsigned a0 = lds_addr(p0);
-  const unsigned a1 = a0 + 4 * (unsigned)pitch * 2;  // keys +4..+7
-  u32x2 lo, hi;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %2\n\t"
-      "ds_read_b64_tr_b16 %1, %3\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(lo), "=&v"(hi)
-      : "v"(a0), "v"(a1)
-      : "memory");
-  __builtin_amdgcn_sched_barrier(0);  // rule 18: keep the MFMA below the wait
-  union {
-    u32x2 u2[2];
-    f16x8 f8;
-  } cvt;
-  cvt.u2[0] = lo;
-  cvt.u2[1] = hi;
-  return cvt.f8;
-}
 
 template <int D, int KT = KVT>  // KT = kv tile
 __global__ __launch_bounds__(256) void attention_kernel(

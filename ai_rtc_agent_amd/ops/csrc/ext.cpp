@@ -82,9 +82,9 @@ ConvProblem conv_problem(ConvKind kind, const torch::Tensor& x,
                          const torch::Tensor& w, const OptTensor& bias,
                          const OptTensor& cbias, const OptTensor& residual,
                          int64_t R, int64_t S, int64_t stride, int64_t pad,
-                         int64_t act, const OptTensor& in_affine,
-                         int64_t in_act, const OptTensor& x2, bool upsample2x,
-                         bool want_q8) {
+                         int64_t pad_hi, int64_t act,
+                         const OptTensor& in_affine, int64_t in_act,
+                         const OptTensor& x2, bool upsample2x, bool want_q8) {
   ConvProblem p;
   AirtcConvArgs& a = p.a;
   const bool x_q8 = kind == CONV_FP8 && x.scalar_type() == torch::kByte;
@@ -99,21 +99,27 @@ ConvProblem conv_problem(ConvKind kind, const torch::Tensor& x,
   TORCH_CHECK(R >= 1 && S >= 1 && stride >= 1 && pad >= 0, "conv needs R, S ",
               ">= 1, stride >= 1, pad >= 0, got ", R, "x", S, " stride ",
               stride, " pad ", pad);
+  // pad_hi: extra zero rows / columns at the bottom / right only
+  TORCH_CHECK(pad_hi >= 0, "conv needs pad_hi >= 0, got ", pad_hi);
+  TORCH_CHECK(kind != CONV_FP8 || pad_hi == 0,
+              "the fp8 conv takes no bottom/right-only padding");
   const int up = upsample2x ? 1 : 0;
   const int64_t B = x.size(0), IC = x.size(3);
   const int64_t H = x.size(1) << up, W = x.size(2) << up;
   const int64_t OC = kind == CONV_TINYIC ? w.size(1) : w.size(0);
   // every extent is an int in the kernels, and so is a tap's coordinate
-  // hi = ho * stride + r - pad < H + 2 * pad: 2^29 each keeps both in range
-  TORCH_CHECK(std::max({B, H, W, IC, OC, R, S, stride, pad}) <= (1 << 29),
+  // hi = ho * stride + r - pad < H + pad + pad_hi (the last tap of the last
+  // output row ends the padded input): 2^29 each keeps both in range
+  TORCH_CHECK(std::max({B, H, W, IC, OC, R, S, stride, pad, pad_hi}) <=
+                  (1 << 29),
               "conv extents must stay within 2^29");
   TORCH_CHECK(IC >= 1, "conv needs input channels");
   // (C++ division truncates towards zero, so test before dividing)
-  TORCH_CHECK(H + 2 * pad >= R && W + 2 * pad >= S, "kernel ", R, "x", S,
-              " is larger than the padded input ", H + 2 * pad, "x",
-              W + 2 * pad);
-  const int64_t HO = (H + 2 * pad - R) / stride + 1;
-  const int64_t WO = (W + 2 * pad - S) / stride + 1;
+  const int64_t HP = H + 2 * pad + pad_hi, WP = W + 2 * pad + pad_hi;
+  TORCH_CHECK(HP >= R && WP >= S, "kernel ", R, "x", S,
+              " is larger than the padded input ", HP, "x", WP);
+  const int64_t HO = (HP - R) / stride + 1;
+  const int64_t WO = (WP - S) / stride + 1;
   const int64_t M = HO * WO;
   // M = HO * WO is an int in every kernel
   TORCH_CHECK(M <= kIntMax, "HO * WO must fit 31 bits");
@@ -204,7 +210,7 @@ ConvProblem conv_problem(ConvKind kind, const torch::Tensor& x,
   a.w = w.data_ptr();
   a.out = q8 ? nullptr : h_ptr_mut(p.out);
   a.B = B, a.H = H, a.W = W, a.IC = IC, a.HO = HO, a.WO = WO, a.OC = OC;
-  a.R = R, a.S = S, a.stride = stride, a.pad = pad;
+  a.R = R, a.S = S, a.stride = stride, a.pad = pad, a.pad_hi = pad_hi;
   a.act = act, a.in_act = in_act, a.path = path, a.IC2 = IC2, a.up = up;
   return p;
 }
@@ -219,12 +225,13 @@ pybind11::tuple conv2d(torch::Tensor x, torch::Tensor w_perm, OptTensor bias,
                        OptTensor cbias, OptTensor residual, int64_t R,
                        int64_t S, int64_t stride, int64_t pad, int64_t act,
                        OptTensor in_affine, int64_t in_act,
-                       int64_t stats_groups, OptTensor x2, bool upsample2x) {
+                       int64_t stats_groups, OptTensor x2, bool upsample2x,
+                       int64_t pad_hi) {
   TORCH_CHECK(stats_groups >= 0 && stats_groups <= kIntMax,
               "stats_groups out of range");
   auto p = conv_problem(CONV_F16, x, w_perm, bias, cbias, residual, R, S,
-                        stride, pad, act, in_affine, in_act, x2, upsample2x,
-                        false);
+                        stride, pad, pad_hi, act, in_affine, in_act, x2,
+                        upsample2x, false);
   AirtcConvArgs& a = p.a;
   torch::Tensor part;
   if (p.empty) return pybind11::make_tuple(p.out, pybind11::none());
@@ -255,10 +262,11 @@ pybind11::tuple conv2d(torch::Tensor x, torch::Tensor w_perm, OptTensor bias,
 torch::Tensor conv2d_tinyic(torch::Tensor x, torch::Tensor w_tiny,
                             OptTensor bias, OptTensor cbias,
                             OptTensor residual, int64_t R, int64_t S,
-                            int64_t stride, int64_t pad, int64_t act) {
+                            int64_t stride, int64_t pad, int64_t act,
+                            int64_t pad_hi) {
   auto p = conv_problem(CONV_TINYIC, x, w_tiny, bias, cbias, residual, R, S,
-                        stride, pad, act, c10::nullopt, 0, c10::nullopt, false,
-                        false);
+                        stride, pad, pad_hi, act, c10::nullopt, 0,
+                        c10::nullopt, false, false);
   if (!p.empty) airtc_conv2d_tinyic(&p.a, cur_stream());
   return p.out;
 }
@@ -274,7 +282,7 @@ torch::Tensor conv2d_fp8(torch::Tensor x, torch::Tensor w_fp8,
                          OptTensor in_affine, int64_t in_act,
                          double out_scale) {
   auto p = conv_problem(CONV_FP8, x, w_fp8, bias, cbias, residual, R, S,
-                        stride, pad, act, in_affine, in_act, c10::nullopt,
+                        stride, pad, 0, act, in_affine, in_act, c10::nullopt,
                         false, out_scale > 0);
   check_operand(dq, x, torch::kFloat, w_fp8.size(0), "dq (f32[OC])");
   if (p.empty) return p.out;
@@ -423,7 +431,10 @@ torch::Tensor attention_bhlc(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   TORCH_CHECK(heads > 0 && C % heads == 0, "channels must split into heads");
   const int d = C / (int)heads;
   TORCH_CHECK(Ck == C && k.size(0) == B, "q/k batch or channel mismatch");
-  TORCH_CHECK(d > 0 && d % 32 == 0 && d <= 160, "head_dim must be padded to one of 32/64/96/128/160");
+  const bool wide = airtc_attention_wide_ok(d) != 0;
+  TORCH_CHECK(d > 0 && d % 32 == 0 && (d <= 160 || wide),
+              "head_dim must be padded to one of 32/64/96/128/160, or be 512 "
+              "(one wide head), got ", d);
   TORCH_CHECK(Lq > 0 && Lk > 0 && B > 0, "attention needs non-empty q and k");
   // the kernel reads rows with 16-byte loads: every row must start on one
   TORCH_CHECK(q.stride(1) % 8 == 0 && k.stride(1) % 8 == 0 &&
@@ -433,6 +444,18 @@ torch::Tensor attention_bhlc(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                   aligned16(v.data_ptr()),
               "q/k/v must start on a 16-byte boundary");
   auto out = torch::empty({B, Lq, C}, q.options());
+  if (wide) {
+    // attention_wide.hip: grid (ceil(Lq / 16), B * heads)
+    TORCH_CHECK((int64_t)B * heads <= kGridYZ,
+                "attention: batch x heads exceeds the grid's y extent");
+    const int rc = airtc_attention_wide(
+        h_ptr(q), h_ptr(k), h_ptr(v), h_ptr_mut(out), B, (int)heads, Lq, Lk, d,
+        q.stride(0), d, q.stride(1), k.stride(0), d, k.stride(1),
+        (long)Lq * C, d, C, (float)scale, cur_stream());
+    TORCH_CHECK(rc == 0, "attention: the wide-head kernel could not reserve "
+                "its LDS (rc=", rc, ")");
+    return out;
+  }
   airtc_attention(h_ptr(q), h_ptr(k), h_ptr(v), h_ptr_mut(out), B, (int)heads,
                   Lq, Lk, d, q.stride(0), d, q.stride(1), k.stride(0), d,
                   k.stride(1), (long)Lq * C, d, C, (float)scale, cur_stream());
@@ -1146,7 +1169,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("in_affine") = pybind11::none(),
         pybind11::arg("in_act") = 0, pybind11::arg("stats_groups") = 0,
         pybind11::arg("x2") = pybind11::none(),
-        pybind11::arg("upsample2x") = false);
+        pybind11::arg("upsample2x") = false, pybind11::arg("pad_hi") = 0);
   m.def("conv2d_tinyic", &conv2d_tinyic,
         "tiny-IC conv (IC <= 4, K <= 36), lanes along OC (NHWC)",
         pybind11::arg("x"), pybind11::arg("w_tiny"),
@@ -1154,7 +1177,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("cbias") = pybind11::none(),
         pybind11::arg("residual") = pybind11::none(), pybind11::arg("R"),
         pybind11::arg("S"), pybind11::arg("stride") = 1,
-        pybind11::arg("pad") = 0, pybind11::arg("act") = 0);
+        pybind11::arg("pad") = 0, pybind11::arg("act") = 0,
+        pybind11::arg("pad_hi") = 0);
   m.def("group_norm_silu", &group_norm_silu, pybind11::arg("x"),
         pybind11::arg("groups"), pybind11::arg("gamma"), pybind11::arg("beta"),
         pybind11::arg("eps"), pybind11::arg("act"),

@@ -170,6 +170,9 @@ typedef struct AirtcConvArgs {
   int B, H, W, IC;  // H, W: the extents the conv sees (upsampled when up)
   int HO, WO, OC;
   int R, S, stride, pad;
+  int pad_hi;   // extra zero rows / columns below and right of the input only
+                // (HO, WO count them); the kernels' hi < H, wi < W predicates
+                // already zero those taps
   int act;      // epilogue: out = act(conv + bias + cbias + residual)
   int in_act;   // with in_aff
   int path;     // airtc_conv2d_splitk_for: 0 = direct, +k = BM128 split-K k,
@@ -223,6 +226,15 @@ void airtc_attention(const uint16_t* q, const uint16_t* k, const uint16_t* v,
                      long q_sb, long q_sh, long q_row, long k_sb, long k_sh,
                      long k_row, long o_sb, long o_sh, long o_row, float scale,
                      hipStream_t s);
+// one wide head (attention_wide.hip): same contract, d with
+// airtc_attention_wide_ok (512). 0, or < 0 when the device refused the
+// kernel's dynamic LDS (nothing launched).
+int airtc_attention_wide_ok(int d);
+int airtc_attention_wide(const uint16_t* q, const uint16_t* k,
+                         const uint16_t* v, uint16_t* out, int B, int H, int Lq,
+                         int Lk, int d, long q_sb, long q_sh, long q_row,
+                         long k_sb, long k_sh, long k_row, long o_sb, long o_sh,
+                         long o_row, float scale, hipStream_t s);
 
 }  // extern "C"
 

@@ -241,8 +241,16 @@ def conv2d_nhwc(
     stats_groups: int | None = None,
     tail: tuple | None = None,
     upsample2x: bool = False,
+    pad_hi: int = 0,
 ) -> torch.Tensor:
     """x: (B,H,W,C) contiguous; weight: (O,I,R,S) [torch layout]; out (B,H',W',O).
+
+    pad_hi: extra zero rows / columns at the bottom and right only, on top
+      of the symmetric `padding` — diffusers' VAE downsample is
+      F.pad(x, (0,1,0,1)) then a stride-2 conv with padding 0, i.e.
+      padding=0, pad_hi=1. H' = (H + 2*padding + pad_hi - R) // stride + 1.
+      GPU: a field of the conv record; the kernels' bounds predicates zero
+      the taps, no padded copy.
 
     tail=(x2, w2, b2): adds the pointwise conv W2·x2 (+ b2) to the result
       before the epilogue — a resnet's 1x1 shortcut. x2 is (B,H',W',C2), w2
@@ -317,7 +325,7 @@ def conv2d_nhwc(
                 bias=None if bias is None else _f32(bias, "_airtc_b32"),
                 cbias=None if channel_bias is None else channel_bias.contiguous(),
                 residual=None if residual is None else residual.contiguous(),
-                R=R, S=S, stride=stride, pad=padding, act=act)
+                R=R, S=S, stride=stride, pad=padding, act=act, pad_hi=pad_hi)
         # Other small-IC convs at large spatial (and the 3/4-channel conv_in
         # layers with AIRTC_CONV_TINYIC=0) measured 129us at 512² on the
         # scalar small-IC kernel; zero-padding
@@ -338,7 +346,7 @@ def conv2d_nhwc(
             return conv2d_nhwc(xp, w_pad, bias, stride, padding, fuse_silu,
                                act=act, residual=residual,
                                channel_bias=channel_bias,
-                               stats_groups=stats_groups)
+                               stats_groups=stats_groups, pad_hi=pad_hi)
         w_perm = _gemm_layout(weight)
         b32 = None if bias is None else _f32(bias, "_airtc_b32")
         if x2 is not None:
@@ -353,7 +361,7 @@ def conv2d_nhwc(
             R=R, S=S, stride=stride, pad=padding, act=act,
             in_affine=None if in_affine is None else in_affine.contiguous(),
             in_act=in_act, stats_groups=stats_groups if want_stats else 0,
-            x2=x2, upsample2x=upsample2x)
+            x2=x2, upsample2x=upsample2x, pad_hi=pad_hi)
         if part is not None:
             # (partials, G, version): the norm ignores them if the tensor
             # was written in place after the conv
@@ -365,6 +373,10 @@ def conv2d_nhwc(
     xc = x.permute(0, 3, 1, 2)
     if upsample2x:
         xc = F.interpolate(xc, scale_factor=2, mode="nearest")
+    if pad_hi:
+        if pad_hi < 0:
+            raise ValueError(f"pad_hi must be >= 0, got {pad_hi}")
+        xc = F.pad(xc, (0, pad_hi, 0, pad_hi))
     y = F.conv2d(xc.float(), weight.float(), None if bias is None else bias.float(),
                  stride=stride, padding=padding)
     if tail is not None:
@@ -565,6 +577,15 @@ def layer_norm(
 # ---------------------------------------------------------------------------
 
 _ATTN_DIMS = (32, 64, 96, 128, 160)
+# one wide head (ops/csrc/attention_wide.hip): served as it is, never a
+# padding target
+_ATTN_WIDE_DIMS = (512,)
+
+
+def attention_serves(head_dim: int) -> bool:
+    """Does a HIP attention kernel take this head width (zero-padded to the
+    next template size where needed)?"""
+    return 0 < head_dim <= max(_ATTN_DIMS) or head_dim in _ATTN_WIDE_DIMS
 
 
 def attention(
@@ -574,7 +595,8 @@ def attention(
     """q: (B, Lq, C); k,v: (B, Lk, C). Returns (B, Lq, C).
 
     GPU: flash-style fused kernel (online softmax, MFMA QK^T and PV,
-    LDS-tiled K/V) — ops/csrc/attention.hip. head_dim % 32 == 0 runs
+    LDS-tiled K/V) — ops/csrc/attention.hip; head_dim 512 (the KL VAE's one
+    wide head) runs ops/csrc/attention_wide.hip. head_dim % 32 == 0 runs
     zero-copy on (b,h)-strided views; other head dims are zero-padded to
     the next supported size (softmax-invariant — but pass the TRUE-dim
     scale when the inputs were padded upstream).
@@ -586,8 +608,13 @@ def attention(
         d = c // num_heads
         if scale is None:
             scale = 1.0 / math.sqrt(d)
-        if d in _ATTN_DIMS:
+        if d in _ATTN_DIMS or d in _ATTN_WIDE_DIMS:
             return ext.attention_bhlc(q, k, v, num_heads, scale)
+        if d > max(_ATTN_DIMS):
+            raise ValueError(
+                f"attention: head_dim {d} has no kernel; supported are up to "
+                f"{max(_ATTN_DIMS)} (padded to one of {_ATTN_DIMS}) and "
+                f"{_ATTN_WIDE_DIMS}")
         dpad = min(x for x in _ATTN_DIMS if x >= d)
 
         def rearrange(t, L):

@@ -31,6 +31,7 @@ def build(
     family: str = "sd15",
     lora: dict | None = None,
     width: int = 512,
+    full_vae: bool = False,
 ) -> str:
     cfg = EngineConfig(
         model_id=model_id,
@@ -38,7 +39,7 @@ def build(
         width=width,
         height=width,
         use_lcm_lora=True,
-        use_tiny_vae=True,
+        use_tiny_vae=not full_vae,
         cfg_type="self",
         mode="img2img",
         lora_dict=lora,
@@ -63,6 +64,10 @@ if __name__ == "__main__":
     p.add_argument("--family", default="sd15", choices=["sd15", "sd21", "sdxl", "tiny"])
     p.add_argument("--width", type=int, default=512)
     p.add_argument("--lora", default=None, help="path:scale[,path:scale...]")
+    p.add_argument("--full-vae", action="store_true",
+                   help="warm a plan with the checkpoint's full AutoencoderKL "
+                        "(use_tiny_vae=False); it is cached beside the "
+                        "tiny-VAE plan, under its own key")
     a = p.parse_args()
     lora = None
     if a.lora:
@@ -70,4 +75,4 @@ if __name__ == "__main__":
         for item in a.lora.split(","):
             path, _, scale = item.partition(":")
             lora[path] = float(scale or 1.0)
-    build(a.model_id, a.family, lora, a.width)
+    build(a.model_id, a.family, lora, a.width, a.full_vae)
