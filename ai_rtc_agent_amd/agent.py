@@ -28,6 +28,7 @@ from typing import Optional
 
 from aiohttp import web
 
+from .engine import LORA_KEEP
 from .media.ice import get_ice_servers, get_link_headers
 from .media.rtc import MediaRelay, PeerConnection, set_udp_port_pool
 from .media.tracks import VideoStreamTrack
@@ -228,6 +229,18 @@ def _checked_config(params) -> dict:
             out[key] = v
     if "canny_low" in out and "canny_high" in out and out["canny_low"] > out["canny_high"]:
         raise ValueError("canny_low must not exceed canny_high")
+    if "lora" in params:
+        # a name the operator loaded, or null for no adapter: never a path or
+        # a bank index
+        v = params["lora"]
+        if v is not None and (not isinstance(v, str) or not v):
+            raise ValueError("lora must be the name of a loaded adapter or null")
+        out["lora"] = v
+    v = params.get("lora_scale")
+    if v is not None:
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError("lora_scale must be a finite number")
+        out["lora_scale"] = float(v)
     return out
 
 
@@ -245,7 +258,11 @@ def _apply_checked(pipeline, cfg: dict) -> None:
     """Apply a type-checked config, key by key. The pipeline itself may
     still reject a value (ValueError): a per-session t_index_list of another
     length, a per-session guidance raise on an engine without
-    runtime_guidance. Keys applied before the rejected one stay applied."""
+    runtime_guidance, a LoRA name nobody loaded (the slot keeps the adapter
+    it had). Keys applied before the rejected one stay applied."""
+    if "lora" in cfg or "lora_scale" in cfg:
+        # first: the key most likely to be refused touches nothing else
+        pipeline.update_lora(cfg.get("lora", LORA_KEEP), cfg.get("lora_scale"))
     if "t_index_list" in cfg:
         pipeline.update_t_index_list(cfg["t_index_list"])
     if "prompt" in cfg:
@@ -372,11 +389,25 @@ async def on_startup(app: web.Application) -> None:
             cfg.use_safety_checker = True
         if app.get("full_vae"):
             cfg.use_tiny_vae = False
+        for key in ("lora_adapters", "lora_max_rank"):
+            if app.get(key) is not None:
+                setattr(cfg, key, app[key])
         cfg.__post_init__()  # validate what was set after construction
+        from .config import lora_adapter_specs
+
+        specs = lora_adapter_specs(app.get("lora_adapter"))
+        if len(specs) > cfg.lora_adapters:
+            raise ValueError(
+                f"{len(specs)} LoRA adapters named, the bank holds "
+                f"{cfg.lora_adapters} (--lora-adapters)")
         st["pool"] = PipelinePool.create(
             model_id=app["model_id"], n_gpus=app["n_gpus"], cfg=cfg,
             streams_per_replica=app.get("streams_per_gpu", 1),
         )
+        if specs:
+            # the names a session may choose among (POST /config "lora")
+            for p in st["pool"].active():
+                p.load_adapters(specs)
     st["ice_servers"] = get_ice_servers() if app["use_turn"] else []
 
 
@@ -422,6 +453,9 @@ def create_app(
     safety_checker: Optional[str] = None,
     safety_adjustment: Optional[float] = None,
     full_vae: bool = False,
+    lora_adapters: Optional[int] = None,
+    lora_max_rank: Optional[int] = None,
+    lora_adapter: Optional[list] = None,
 ) -> web.Application:
     app = web.Application(middlewares=[cors_middleware])
     app["model_id"] = model_id
@@ -450,6 +484,11 @@ def create_app(
     app["safety_adjustment"] = safety_adjustment
     # False: EngineConfig default (AIRTC_TINY_VAE); True: the full AutoencoderKL
     app["full_vae"] = full_vae
+    # None: EngineConfig defaults (AIRTC_LORA_ADAPTERS, AIRTC_LORA_MAX_RANK)
+    # and $AIRTC_LORA_ADAPTER_FILES; NAME=PATH[:SCALE] strings otherwise
+    app["lora_adapters"] = lora_adapters
+    app["lora_max_rank"] = lora_max_rank
+    app["lora_adapter"] = lora_adapter
     app["state"] = {
         "pcs": set(),
         "source_track": None,
@@ -560,6 +599,22 @@ def build_parser() -> argparse.ArgumentParser:
                              "stricter; operator-only, not reachable from "
                              "POST /config (default: "
                              "$AIRTC_SAFETY_ADJUSTMENT or 0)")
+    parser.add_argument("--lora-adapters", type=int, default=None,
+                        help="capacity of the per-session LoRA bank, 0..64; "
+                             "0 = off. Sessions of a batched replica then "
+                             "choose their own adapter through POST /config "
+                             "\"lora\" without a graph re-capture (default: "
+                             "$AIRTC_LORA_ADAPTERS or 0)")
+    parser.add_argument("--lora-max-rank", type=int, default=None,
+                        help="largest adapter rank the bank accepts, 1..64 "
+                             "(default: $AIRTC_LORA_MAX_RANK or 32)")
+    parser.add_argument("--lora-adapter", action="append", default=None,
+                        metavar="NAME=PATH[:SCALE]",
+                        help="load this adapter file into the bank at "
+                             "start-up under NAME; repeatable, at most "
+                             "--lora-adapters of them. Clients choose among "
+                             "these names and never supply a path (default: "
+                             "$AIRTC_LORA_ADAPTER_FILES, comma-separated)")
     parser.add_argument("--streams-per-gpu", type=int, default=1,
                         help="multi-stream batched serving: sessions per "
                              "GPU batched through one engine (fbs=K; "
@@ -614,6 +669,12 @@ def main() -> None:
                 os.environ[env] = str(getattr(args, flag))
         if args.full_vae:
             os.environ["AIRTC_TINY_VAE"] = "0"
+        for flag, env in (("lora_adapters", "AIRTC_LORA_ADAPTERS"),
+                          ("lora_max_rank", "AIRTC_LORA_MAX_RANK")):
+            if getattr(args, flag) is not None:
+                os.environ[env] = str(getattr(args, flag))
+        if args.lora_adapter:
+            os.environ["AIRTC_LORA_ADAPTER_FILES"] = ",".join(args.lora_adapter)
         fe = WorkerFrontend(args.workers, model_id=args.model_id,
                             family=args.family, resolution=args.resolution,
                             pin_gpu=torch.cuda.is_available(),
@@ -636,7 +697,10 @@ def main() -> None:
                      canny_reach=args.canny_reach,
                      safety_checker=args.safety_checker,
                      safety_adjustment=args.safety_adjustment,
-                     full_vae=args.full_vae)
+                     full_vae=args.full_vae,
+                     lora_adapters=args.lora_adapters,
+                     lora_max_rank=args.lora_max_rank,
+                     lora_adapter=args.lora_adapter)
     web.run_app(app, host=args.host, port=args.port)
 
 

@@ -84,6 +84,14 @@ def _env_float(name: str, default: float) -> float:
 #                                        AutoencoderKL (models/vae_kl.py):
 #                                        sharper decode at about a third of the
 #                                        frame rate. sd15 / sd21 only
+# AIRTC_LORA_ADAPTERS (0..64)         -> EngineConfig.lora_adapters: capacity
+#                                        of the per-session adapter bank; 0
+#                                        (default) = the feature is off
+# AIRTC_LORA_ADAPTER_FILES            -> NAME=PATH[:SCALE],... the adapters the
+#                                        agent loads into bank indices 0, 1, ...
+#                                        at start-up (--lora-adapter)
+# AIRTC_LORA_MAX_RANK (1..64)         -> EngineConfig.lora_max_rank: largest
+#                                        adapter rank the bank accepts
 
 
 def engines_cache_dir() -> str:
@@ -121,6 +129,39 @@ def media_yuv() -> bool:
     the engine converts them on the GPU and returns I420 for the encoder
     (frame format: ops/interface.py)."""
     return _env_bool("AIRTC_MEDIA_YUV", False)
+
+
+def parse_lora_adapter(spec: str) -> tuple:
+    """--lora-adapter NAME=PATH[:SCALE] -> (name, path, scale). The scale is
+    what follows the LAST colon when that parses as a number."""
+    name, eq, rest = spec.partition("=")
+    if not eq or not name or not rest:
+        raise ValueError(f"a LoRA adapter is NAME=PATH[:SCALE], got {spec!r}")
+    path, colon, tail = rest.rpartition(":")
+    scale = 1.0
+    if colon:
+        try:
+            scale = float(tail)
+        except ValueError:
+            path = rest
+    else:
+        path = rest
+    if not path or not math.isfinite(scale):
+        raise ValueError(f"a LoRA adapter is NAME=PATH[:SCALE], got {spec!r}")
+    return name, path, scale
+
+
+def lora_adapter_specs(specs=None) -> list:
+    """The adapters to load at start-up: the given NAME=PATH[:SCALE] strings,
+    else $AIRTC_LORA_ADAPTER_FILES (comma-separated), parsed; names unique."""
+    if specs is None:
+        env = os.environ.get("AIRTC_LORA_ADAPTER_FILES", "")
+        specs = [s for s in env.split(",") if s.strip()]
+    out = [parse_lora_adapter(s.strip()) for s in specs]
+    names = [n for n, _, _ in out]
+    if len(set(names)) != len(names):
+        raise ValueError(f"LoRA adapter names must be unique, got {names}")
+    return out
 
 
 OUTPUT_FORMATS = ("rgb", "i420")
@@ -261,7 +302,29 @@ class EngineConfig:
     canny_high: int = field(default_factory=lambda: _env_int("AIRTC_CANNY_HIGH", 200))
     canny_reach: int = field(default_factory=lambda: _env_int("AIRTC_CANNY_REACH", 16))
 
+    # per-session LoRA under batched serving: lora_adapters > 0 keeps that
+    # many adapters unfused in a device-resident bank (models/lora.py:
+    # LoraBank) and adds scale_b * (x_b A_a^T) B_a^T to every transformer
+    # projection inside the captured graph (ops.lora_delta_), adapter and
+    # scale read per batch row from a table engine.update_lora rewrites in
+    # place. 0 (default): no bank, no launch, the graphs of before.
+    # lora_max_rank bounds an adapter's rank (the bank rounds it up to 16,
+    # 32 or 64). Not with use_fp8 (below).
+    lora_adapters: int = field(default_factory=lambda: _env_int("AIRTC_LORA_ADAPTERS", 0))
+    lora_max_rank: int = field(default_factory=lambda: _env_int("AIRTC_LORA_MAX_RANK", 32))
+
     def __post_init__(self) -> None:
+        for name, lo, hi in (("lora_adapters", 0, 64), ("lora_max_rank", 1, 64)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"{name} must be an int, got {v!r}")
+            if not lo <= v <= hi:
+                raise ValueError(f"{name} must be in [{lo}, {hi}], got {v}")
+        if self.lora_adapters > 0 and self.use_fp8:
+            raise ValueError(
+                "lora_adapters > 0 is not available with use_fp8: the fp8 "
+                "tier's activation scales are calibrated once, and nobody has "
+                "measured them against a per-slot weight change")
         if not self.use_tiny_vae and self.model_family in ("sdxl", "tiny_xl"):
             raise ValueError(
                 f"use_tiny_vae=False is not available for model_family="

@@ -51,6 +51,10 @@ def _unet_config_for(family: str) -> UNetConfig:
     }[family]()
 
 
+# update_lora(adapter=LORA_KEEP, scale=...): the scale alone, adapter as it is
+LORA_KEEP = object()
+
+
 class StreamDiffusionEngine:
     def __init__(
         self,
@@ -61,6 +65,8 @@ class StreamDiffusionEngine:
         safety_checker: Optional[torch.nn.Module] = None,
     ) -> None:
         self.cfg = cfg
+        # per-session adapter bank, built by prepare() when cfg.lora_adapters > 0
+        self._lora_bank = None
         if cfg.output_format not in ("rgb", "i420"):
             raise ValueError(
                 f"output_format must be 'rgb' or 'i420', got {cfg.output_format!r}")
@@ -336,6 +342,7 @@ class StreamDiffusionEngine:
         self._pipelined = False
         self._last_done = None
         self._prepared = True
+        self._prepare_lora()
         self._refresh_static_kv()
         self._ts_unet_cache = None
         self._refresh_temb_static()
@@ -433,6 +440,154 @@ class StreamDiffusionEngine:
         self._graph = None  # re-capture lazily with the new weights
 
     # ------------------------------------------------------------------
+    # per-session LoRA (cfg.lora_adapters > 0): an unfused adapter bank the
+    # captured graph reads through a per-row (adapter, scale) table. Loading
+    # a file into a bank index and pointing a slot at an index are in-place
+    # writes: no re-capture, no refresh_weights, no device-wide synchronise.
+    # The global load_lora path above is separate and unchanged.
+    # ------------------------------------------------------------------
+    def _prepare_lora(self) -> None:
+        cfg = self.cfg
+        if cfg.lora_adapters <= 0:
+            return
+        if self._lora_bank is None:
+            from ..models.lora import LoraBank
+
+            self._lora_bank = LoraBank(self.unet, cfg.lora_adapters,
+                                       cfg.lora_max_rank)
+            self._lora_names: dict = {}   # name -> bank index
+            self._lora_loads: dict = {}   # name -> times loaded
+            self._lora_default = (None, 1.0)
+            # _slot_ctl was filled before the bank existed
+            for c in self._slot_ctl:
+                c["lora"], c["lora_scale"] = self._lora_default
+        # the largest UNet batch of any layout: full doubles the rows,
+        # initialize adds fbs; every layout keeps row % fbs == slot, so one
+        # table serves them all by its prefix
+        rows = 2 * cfg.denoising_steps * cfg.frame_buffer_size
+        ra, rs = self._lora_bank.rows
+        if ra.shape[0] != rows:
+            self._lora_bank.set_rows(
+                torch.full((rows,), -1, dtype=torch.int32, device=self.device),
+                torch.ones(rows, dtype=torch.float32, device=self.device))
+        self._write_lora_rows(refresh_kv=False)
+
+    def _lora_name_of(self, index):
+        for n, i in self._lora_names.items():
+            if i == index:
+                return n
+        return None
+
+    def _write_lora_rows(self, slot: Optional[int] = None,
+                         refresh_kv: bool = True) -> None:
+        """The (adapter, scale) of one slot (None: of every slot) into its
+        rows of the tables, and with them its static cross-attention K|V,
+        which carry the to_k / to_v deltas. Scalar fills: nothing is
+        uploaded, and no other slot's rows are touched."""
+        fbs = self.cfg.frame_buffer_size
+        ra, rs = self._lora_bank.rows
+        with self._row_writes():
+            for s in (range(fbs) if slot is None else [slot]):
+                c = self._slot_ctl[s]
+                slot_rows(ra, s, fbs).fill_(-1 if c["lora"] is None else c["lora"])
+                slot_rows(rs, s, fbs).fill_(c["lora_scale"])
+            if not refresh_kv:
+                return
+            if slot is None:
+                self._refresh_static_kv()
+                return
+            # row `slot` of the embeddings is one of the slot's rows
+            self._write_slot_kv(self._embeds_batch[slot:slot + 1], slot)
+            if self._layout() == "full":
+                self._write_slot_kv(self._embeds_full[slot:slot + 1], slot,
+                                    uncond=True)
+
+    def _resolve_adapter(self, adapter):
+        """None, a bank index or a loaded name -> None or a loaded index."""
+        bank = self._lora_bank
+        if adapter is None:
+            return None
+        if isinstance(adapter, str):
+            if adapter not in self._lora_names:
+                raise ValueError(
+                    f"unknown LoRA {adapter!r}; loaded: {sorted(self._lora_names)}")
+            return self._lora_names[adapter]
+        if isinstance(adapter, bool) or not isinstance(adapter, int) \
+                or not 0 <= adapter < bank.n_adapters:
+            raise ValueError(
+                f"adapter must be None, a loaded name or a bank index in "
+                f"[0, {bank.n_adapters}), got {adapter!r}")
+        if not bank.loaded[adapter]:
+            raise ValueError(f"bank index {adapter} holds no adapter")
+        return adapter
+
+    def _require_bank(self):
+        if self._lora_bank is None:
+            raise ValueError(
+                "per-session LoRA is off: build the engine with "
+                "lora_adapters > 0 (AIRTC_LORA_ADAPTERS)")
+        return self._lora_bank
+
+    @torch.no_grad()
+    def load_adapter(self, index: int, path_or_sd, scale: float = 1.0,
+                     name: Optional[str] = None) -> dict:
+        """Load an adapter file (kohya, diffusers/PEFT or own-path keys) into
+        bank index `index`, in place, under the name `name`. Slots that point
+        at the index show the new adapter from the next frame. Returns the
+        loader's counts (LoraBank.load).
+
+        Like every update_* call it must come from the thread that calls the
+        engine, never concurrently with __call__: the bank is rewritten by
+        one copy per target on the denoise stream, and a replay enqueued
+        between two of them would read an adapter half old, half new."""
+        assert self._prepared, "call prepare() first"
+        bank = self._require_bank()
+        if name is not None and (not isinstance(name, str) or not name):
+            raise ValueError(f"name must be a non-empty string, got {name!r}")
+        if name is not None and self._lora_names.get(name, index) != index:
+            raise ValueError(
+                f"LoRA name {name!r} already names bank index "
+                f"{self._lora_names[name]}")
+        sd = load_lora_file(path_or_sd) if isinstance(path_or_sd, str) else path_or_sd
+        used = any(c["lora"] == index for c in self._slot_ctl)
+        counts = bank.load(index, sd, scale=scale, ordered=self._row_writes,
+                           after=self._refresh_static_kv if used else None)
+        for n in [n for n, i in self._lora_names.items() if i == index]:
+            del self._lora_names[n]
+        if name is not None:
+            self._lora_names[name] = index
+            self._lora_loads[name] = self._lora_loads.get(name, 0) + 1
+        return counts
+
+    @torch.no_grad()
+    def update_lora(self, adapter=None, scale: Optional[float] = None,
+                    slot: Optional[int] = None) -> None:
+        """Point a slot (slot=None: every slot, and the default reset_slot()
+        restores) at an adapter: a bank index, a loaded name, None for no
+        adapter, or LORA_KEEP to change the scale alone. scale=None keeps
+        the slot's scale. Everything is validated before the first write."""
+        self._check_slot(slot)
+        self._require_bank()
+        keep = adapter is LORA_KEEP
+        index = None if keep else self._resolve_adapter(adapter)
+        if scale is not None:
+            if isinstance(scale, bool) or not isinstance(scale, (int, float)) \
+                    or not math.isfinite(scale):
+                raise ValueError(f"lora scale must be a finite number, got {scale!r}")
+            scale = float(scale)
+        for s in (range(self.cfg.frame_buffer_size) if slot is None else [slot]):
+            c = self._slot_ctl[s]
+            if not keep:
+                c["lora"] = index
+            if scale is not None:
+                c["lora_scale"] = scale
+        if slot is None:
+            self._lora_default = (
+                self._lora_default[0] if keep else index,
+                self._lora_default[1] if scale is None else scale)
+        self._write_lora_rows(slot)
+
+    # ------------------------------------------------------------------
     # runtime config updates (POST /config + datachannel; SURVEY.md §3.5)
     #
     # Every updater takes slot=None (every slot: the replica-wide update,
@@ -453,6 +608,8 @@ class StreamDiffusionEngine:
             d["canny_high"] = int(cfg.canny_high)
         if self._clip_safety:
             d["safety_adjustment"] = float(cfg.safety_adjustment)
+        if self._lora_bank is not None:
+            d["lora"], d["lora_scale"] = self._lora_default
         return d
 
     def _set_ctl(self, slot: Optional[int], **kw) -> None:
@@ -507,6 +664,15 @@ class StreamDiffusionEngine:
 
     def _write_slot_kv(self, emb: torch.Tensor, slot: Optional[int],
                        uncond: bool = False) -> None:
+        if self._lora_bank is not None and slot is None:
+            # the slots' adapters may differ: one K|V per slot
+            for s in range(self.cfg.frame_buffer_size):
+                self._write_slot_kv(emb, s, uncond)
+            return
+        self._write_slot_kv_rows(emb, slot, uncond)
+
+    def _write_slot_kv_rows(self, emb: torch.Tensor, slot: Optional[int],
+                            uncond: bool) -> None:
         """K|V of ONE prompt (a 1-row GEMM per cross-attention layer) into
         the slot's rows of every static_kv. In the full layout the prompt
         owns the cond half and the negative prompt (uncond=True) the uncond
@@ -520,7 +686,10 @@ class StreamDiffusionEngine:
             if layout == "full":
                 half = kv.shape[0] // 2
                 kv = kv[:half] if uncond else kv[half:]
-            slot_rows(kv, slot, fbs).copy_(m.compute_kv(emb))
+            # table row `slot` is one of the slot's rows (row % fbs == slot)
+            rows = (None if self._lora_bank is None else
+                    tuple(t[slot:slot + 1] for t in self._lora_bank.rows))
+            slot_rows(kv, slot, fbs).copy_(m.compute_kv(emb, lora_rows=rows))
 
     @torch.no_grad()
     def update_prompt(self, prompt: str, slot: Optional[int] = None) -> None:
@@ -738,6 +907,9 @@ class StreamDiffusionEngine:
                 self.update_canny(c["canny_low"], c["canny_high"], slot)
             if self._clip_safety and c["safety_adjustment"] != old["safety_adjustment"]:
                 self.update_safety(c["safety_adjustment"], slot)
+            if self._lora_bank is not None and (c["lora"], c["lora_scale"]) != (
+                    old["lora"], old["lora_scale"]):
+                self.update_lora(adapter=c["lora"], scale=c["lora_scale"], slot=slot)
 
     @staticmethod
     def _tensors_of(coeff: dict) -> list:
@@ -808,6 +980,9 @@ class StreamDiffusionEngine:
             self.update_canny(d["canny_low"], d["canny_high"], slot)
         if self._clip_safety and c["safety_adjustment"] != d["safety_adjustment"]:
             self.update_safety(d["safety_adjustment"], slot)
+        if self._lora_bank is not None and (c["lora"], c["lora_scale"]) != (
+                d["lora"], d["lora_scale"]):
+            self.update_lora(adapter=d["lora"], scale=d["lora_scale"], slot=slot)
         self._prev_out = None
         self._prev_sizes = None
         if slot < len(self._out_size):
@@ -1493,6 +1668,18 @@ class StreamDiffusionEngine:
                 # per slot; the one device read, made here and never in the
                 # frame path
                 "frames_flagged": self._safety_count.tolist(),
+            }
+        if self._lora_bank is not None:
+            d["lora"] = {
+                "capacity": self.cfg.lora_adapters,
+                "max_rank": self.cfg.lora_max_rank,
+                # name -> bank index and how often the name was loaded
+                "loaded": {n: {"index": i, "loads": self._lora_loads.get(n, 0)}
+                           for n, i in self._lora_names.items()},
+                # per slot, as last written (host-side copies)
+                "slots": [{"lora": self._lora_name_of(c["lora"]),
+                           "index": c["lora"], "scale": c["lora_scale"]}
+                          for c in self._slot_ctl],
             }
         if self.cfg.use_fp8:
             d["fp8"] = {

@@ -31,13 +31,17 @@ from ..config import EngineConfig, engines_cache_dir
 
 
 def plan_dir(model_id: str, cache_root: Optional[str] = None,
-             tiny_vae: bool = True) -> str:
+             tiny_vae: bool = True, lora_adapters: int = 0) -> str:
     # naming contract: engines--<model-id with '/' -> '--'>; a plan built
     # with the checkpoint's full AutoencoderKL (use_tiny_vae=False) holds
     # other VAE weights under the same file name, so it gets its own key
     name = "engines--" + model_id.replace("/", "--")
     if not tiny_vae:
         name += "--full-vae"
+    # an engine with a per-session adapter bank (lora_adapters > 0) runs other
+    # graphs over the same weights: its own key as well
+    if lora_adapters > 0:
+        name += "--slot-lora"
     return os.path.join(cache_root or engines_cache_dir(), name)
 
 
@@ -49,7 +53,8 @@ def _cfg_dict(cfg: EngineConfig) -> dict:
 def save_plan(engine, cache_root: Optional[str] = None) -> str:
     from safetensors.torch import save_file
 
-    out = plan_dir(engine.cfg.model_id, cache_root, engine.cfg.use_tiny_vae)
+    out = plan_dir(engine.cfg.model_id, cache_root, engine.cfg.use_tiny_vae,
+                   engine.cfg.lora_adapters)
     os.makedirs(out, exist_ok=True)
 
     def dump(module: torch.nn.Module, name: str) -> None:
@@ -77,7 +82,7 @@ def load_plan(cfg: EngineConfig, cache_root: Optional[str] = None):
     ladder, lib/wrapper.py:611-615)."""
     from safetensors.torch import load_file
 
-    d = plan_dir(cfg.model_id, cache_root, cfg.use_tiny_vae)
+    d = plan_dir(cfg.model_id, cache_root, cfg.use_tiny_vae, cfg.lora_adapters)
     if not os.path.exists(os.path.join(d, "plan.json")):
         return None
     from .engine import StreamDiffusionEngine
@@ -113,7 +118,7 @@ def kernel_plan_for(cfg: EngineConfig) -> dict:
     Recorded for inspection + warm-start; the runtime makes the same
     decisions deterministically (ops/csrc/conv2d.hip:airtc_conv2d_splitk_for)."""
     lat = cfg.latent_height
-    return {
+    plan = {
         "resolution": [cfg.height, cfg.width],
         "latent": [lat, cfg.latent_width],
         "unet_batch": cfg.unet_batch,
@@ -127,3 +132,7 @@ def kernel_plan_for(cfg: EngineConfig) -> dict:
         },
         "hip_graph": cfg.use_hip_graph,
     }
+    if cfg.lora_adapters > 0:
+        plan["slot_lora"] = {"adapters": cfg.lora_adapters,
+                             "max_rank": cfg.lora_max_rank}
+    return plan

@@ -118,7 +118,12 @@ class Linear(nn.Module):
         self.bias = nn.Parameter(torch.zeros(dout)) if bias else None
 
     def forward(self, x: torch.Tensor, residual: torch.Tensor | None = None) -> torch.Tensor:
-        return ops.linear(x, self.weight, self.bias, residual=residual)
+        y = ops.linear(x, self.weight, self.bias, residual=residual)
+        # per-session adapter bank (models/lora.py:LoraBank), absent by default
+        lora = getattr(self, "_lora", None)
+        if lora is not None:
+            lora.apply_(y, x)
+        return y
 
 
 class Conv2d(nn.Module):
@@ -294,18 +299,26 @@ class CrossAttention(nn.Module):
             self, name, lambda: build().detach().to(ref.device, ref.dtype),
             key=(ref.device, ref.dtype))
 
-    def compute_kv(self, ctx: torch.Tensor) -> torch.Tensor:
+    def compute_kv(self, ctx: torch.Tensor, lora_rows=None) -> torch.Tensor:
         """Fused K|V projection of a context. The engine calls this at
         prepare()/update_prompt() to PRECOMPUTE text K/V into a static
         buffer (`static_kv`): cross-attention K/V depend only on the prompt,
         so the per-frame graph skips these GEMMs entirely (the reference
         keeps prompt encoding out of its TRT hot path the same way,
-        lib/pipeline.py:44-45)."""
+        lib/pipeline.py:44-45). With an adapter bank the rows' to_k / to_v
+        deltas go in here: lora_rows = (row_adapter, row_scale) of ctx's
+        rows, default the bank's tables for a full UNet batch."""
         wkv = self._cached_w(
             "_wkv", ctx,
             lambda: torch.cat([self._pad_heads(p.weight) for p in (self.to_k, self.to_v)]),
         )
-        return ops.linear(ctx, wkv)
+        kv = ops.linear(ctx, wkv)
+        n = self.heads * self.dpad
+        for i, p in enumerate((self.to_k, self.to_v)):
+            lora = getattr(p, "_lora", None)
+            if lora is not None:
+                lora.apply_(kv, ctx, i * n, rows=lora_rows)
+        return kv
 
     def forward(
         self,
@@ -319,10 +332,18 @@ class CrossAttention(nn.Module):
                 lambda: torch.cat([self._pad_heads(p.weight) for p in (self.to_q, self.to_k, self.to_v)]),
             )
             qkv = ops.linear(x, wqkv)
+            for i, p in enumerate((self.to_q, self.to_k, self.to_v)):
+                lora = getattr(p, "_lora", None)
+                if lora is not None:
+                    # three calls on the shared x, one column range each
+                    lora.apply_(qkv, x, i * self.heads * self.dpad)
             q, k, v = qkv.chunk(3, dim=-1)
         else:
             wq = self._cached_w("_wq", x, lambda: self._pad_heads(self.to_q.weight))
             q = ops.linear(x, wq)
+            lora = getattr(self.to_q, "_lora", None)
+            if lora is not None:
+                lora.apply_(q, x)
             kv = getattr(self, "static_kv", None)
             if kv is None:
                 kv = self.compute_kv(ctx)
@@ -335,7 +356,11 @@ class CrossAttention(nn.Module):
                 self.to_out.weight.t().contiguous()
             ).reshape(self.heads * self.dpad, -1).t().contiguous(),
         )
-        return ops.linear(o, wout, self.to_out.bias, residual=residual)
+        y = ops.linear(o, wout, self.to_out.bias, residual=residual)
+        lora = getattr(self.to_out, "_lora", None)
+        if lora is not None:
+            lora.apply_(y, o)
+        return y
 
 
 class FeedForwardGEGLU(nn.Module):

@@ -814,6 +814,71 @@ torch::Tensor blank_flagged_(torch::Tensor img, torch::Tensor flags) {
   return img;
 }
 
+// --- per-row LoRA delta (lora.hip) --------------------------------------
+struct LoraShape {
+  int Bt, L, K, N, Ny, R, n_adapters;
+};
+
+LoraShape check_lora_delta(const torch::Tensor& y, const torch::Tensor& x,
+                           const torch::Tensor& A, const torch::Tensor& B,
+                           const torch::Tensor& row_adapter,
+                           const torch::Tensor& row_scale,
+                           int64_t col_offset) {
+  check_operand(x, x, torch::kHalf, "lora_delta_: x");
+  check_operand(y, x, torch::kHalf, "lora_delta_: y");
+  check_operand(A, x, torch::kHalf, "lora_delta_: A");
+  check_operand(B, x, torch::kHalf, "lora_delta_: B");
+  TORCH_CHECK(x.dim() == 3 && y.dim() == 3 && A.dim() == 3 && B.dim() == 3,
+              "lora_delta_: x (Bt, L, K), y (Bt, L, Ny), A (n, R, K), "
+              "B (n, N, R)");
+  const int64_t Bt = x.size(0), L = x.size(1), K = x.size(2);
+  const int64_t Ny = y.size(2), n = A.size(0), R = A.size(1), N = B.size(1);
+  TORCH_CHECK(y.size(0) == Bt && y.size(1) == L,
+              "lora_delta_: y must have x's batch and tokens, got ",
+              y.sizes(), " for x ", x.sizes());
+  TORCH_CHECK(A.size(2) == K, "lora_delta_: A must be (n, R, K=", K,
+              "), got ", A.sizes());
+  TORCH_CHECK(n >= 1 && B.size(0) == n && B.size(2) == R,
+              "lora_delta_: B must be (n=", n, ", N, R=", R, "), got ",
+              B.sizes());
+  check_operand(row_adapter, x, torch::kInt, Bt, "lora_delta_: row_adapter");
+  check_operand(row_scale, x, torch::kFloat, Bt, "lora_delta_: row_scale");
+  TORCH_CHECK(Bt >= 1 && Bt <= kGridYZ && L >= 1,
+              "lora_delta_: 1..", kGridYZ, " rows of at least one token");
+  TORCH_CHECK(R == 16 || R == 32 || R == 64,
+              "lora_delta_: R must be 16, 32 or 64, got ", R);
+  TORCH_CHECK(K >= 32 && K % 32 == 0, "lora_delta_: K % 32 != 0, got ", K);
+  TORCH_CHECK(N >= 16 && N % 16 == 0, "lora_delta_: N % 16 != 0, got ", N);
+  TORCH_CHECK(col_offset >= 0 && col_offset % 16 == 0,
+              "lora_delta_: col_offset % 16 != 0, got ", col_offset);
+  TORCH_CHECK(col_offset + N <= Ny, "lora_delta_: columns [", col_offset,
+              ", ", col_offset + N, ") do not fit y's ", Ny);
+  // y is read and written four columns (8 bytes) at a time
+  TORCH_CHECK(Ny % 4 == 0, "lora_delta_: Ny % 4 != 0, got ", Ny);
+  TORCH_CHECK(x.numel() <= kIntMax && y.numel() <= kIntMax &&
+                  A.numel() <= kIntMax && B.numel() <= kIntMax,
+              "lora_delta_: x, y, A and B must each hold fewer than 2^31 "
+              "values");
+  TORCH_CHECK(aligned16(x.data_ptr()) && aligned16(A.data_ptr()) &&
+                  aligned16(B.data_ptr()) &&
+                  ((uintptr_t)y.data_ptr() & 7) == 0,
+              "lora_delta_: x, A, B must be 16-byte and y 8-byte aligned");
+  return {(int)Bt, (int)L, (int)K, (int)N, (int)Ny, (int)R, (int)n};
+}
+
+torch::Tensor lora_delta_(torch::Tensor y, torch::Tensor x, torch::Tensor A,
+                          torch::Tensor B, torch::Tensor row_adapter,
+                          torch::Tensor row_scale, int64_t col_offset) {
+  const LoraShape d =
+      check_lora_delta(y, x, A, B, row_adapter, row_scale, col_offset);
+  const int rc = airtc_lora_delta(
+      h_ptr(x), h_ptr_mut(y), h_ptr(A), h_ptr(B), row_adapter.data_ptr<int>(),
+      row_scale.data_ptr<float>(), d.Bt, d.L, d.K, d.N, d.Ny, d.R,
+      (int)col_offset, d.n_adapters, cur_stream());
+  TORCH_CHECK(rc == 0, "lora_delta_: the launcher refused the shape");
+  return y;
+}
+
 // --- software H.264 baseline-intra codec (h264sw.cpp) -----------------
 extern "C" {
 void* airtc_h264enc_create(int w, int h);
@@ -1231,6 +1296,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "class token -> (flags i32, scores f32); counters += flags");
   m.def("blank_flagged_", &blank_flagged_,
         "flagged frames -> -1, in place");
+  m.def("lora_delta_", &lora_delta_, pybind11::arg("y"), pybind11::arg("x"),
+        pybind11::arg("A"), pybind11::arg("B"), pybind11::arg("row_adapter"),
+        pybind11::arg("row_scale"), pybind11::arg("col_offset") = 0);
   m.def("conv2d_fp8", &conv2d_fp8,
         "fp8 e4m3 implicit-GEMM conv2d on the MX-scaled MFMA (NHWC)",
         pybind11::arg("x"), pybind11::arg("w_fp8"), pybind11::arg("dq"),

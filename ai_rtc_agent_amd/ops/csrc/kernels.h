@@ -236,6 +236,21 @@ int airtc_attention_wide(const uint16_t* q, const uint16_t* k,
                          long k_sb, long k_sh, long k_row, long o_sb, long o_sh,
                          long o_row, float scale, hipStream_t s);
 
+// per-row LoRA delta (lora.hip) ---------------------------------------------
+// y[b, :, col_offset : col_offset+N] += row_scale[b] * (x[b] . A[a]^T) . B[a]^T
+// in place, a = row_adapter[b]; rows with a < 0 (or a >= n_adapters) are not
+// read or written. x (Bt, L, K), y (Bt, L, Ny), A (n_adapters, R, K),
+// B (n_adapters, N, R), f16, x / A / B 16-byte and y 8-byte aligned. Needs
+// K % 32 == 0, N % 16 == 0, col_offset % 16 == 0, col_offset + N <= Ny,
+// Ny % 4 == 0, R in {16, 32, 64}, Bt <= 65535; the caller (ext.cpp) also keeps
+// every element count within 31 bits. Returns -1 and launches nothing
+// otherwise.
+int airtc_lora_delta(const uint16_t* x, uint16_t* y, const uint16_t* A,
+                     const uint16_t* B, const int* row_adapter,
+                     const float* row_scale, int Bt, int L, int K, int N,
+                     int Ny, int R, int col_offset, int n_adapters,
+                     hipStream_t s);
+
 }  // extern "C"
 
 // vcn ------------------------------------------------------------------------

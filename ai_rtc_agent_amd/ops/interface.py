@@ -1642,3 +1642,49 @@ def blank_flagged_(img: torch.Tensor, flags: torch.Tensor) -> torch.Tensor:
         return _require_ext().blank_flagged_(img, flags)
     return img.masked_fill_(
         (flags != 0).view(-1, *([1] * (img.dim() - 1))), -1.0)
+
+
+def lora_delta_(y: torch.Tensor, x: torch.Tensor, A: torch.Tensor,
+                B: torch.Tensor, row_adapter: torch.Tensor,
+                row_scale: torch.Tensor, col_offset: int = 0) -> torch.Tensor:
+    """In place: y[b, :, col_offset : col_offset+N] += row_scale[b] *
+    (x[b] @ A[a].T) @ B[a].T with a = row_adapter[b]; rows with a < 0 or
+    a >= n and every other column of y are not written. x (Bt, L, K), y (Bt, L, Ny),
+    A (n, R, K) "down", B (n, N, R) "up" (alpha/rank folded in), row_adapter
+    (Bt,) int32, row_scale (Bt,) f32. Adapter and scale are read on the
+    device: no host sync, and a captured graph follows later table writes.
+
+    The torch form below defines the op: the intermediate is rounded to x's
+    dtype, the scale multiplies the f32 second product, and the sum with y
+    is rounded once. The HIP kernel (f16) refuses K % 32, N % 16,
+    col_offset % 16, Ny % 4 != 0 and R outside {16, 32, 64}."""
+    if x.dim() != 3 or y.dim() != 3 or A.dim() != 3 or B.dim() != 3:
+        raise ValueError("lora_delta_: x (Bt, L, K), y (Bt, L, Ny), "
+                         "A (n, R, K), B (n, N, R)")
+    Bt, L, K = x.shape
+    n, R, N = A.shape[0], A.shape[1], B.shape[1]
+    if (y.shape[:2] != x.shape[:2] or A.shape[2] != K
+            or B.shape[0] != n or B.shape[2] != R):
+        raise ValueError(
+            f"lora_delta_: shapes disagree: x {tuple(x.shape)}, y "
+            f"{tuple(y.shape)}, A {tuple(A.shape)}, B {tuple(B.shape)}")
+    if col_offset < 0 or col_offset + N > y.shape[2]:
+        raise ValueError(
+            f"lora_delta_: columns [{col_offset}, {col_offset + N}) do not "
+            f"fit y's {y.shape[2]}")
+    if (row_adapter.dtype != torch.int32 or row_adapter.shape != (Bt,)
+            or row_scale.dtype != torch.float32 or row_scale.shape != (Bt,)):
+        raise ValueError("lora_delta_: row_adapter (Bt,) int32 and "
+                         "row_scale (Bt,) float32")
+    if _use_hip(x):
+        return _require_ext().lora_delta_(y, x, A, B, row_adapter, row_scale,
+                                          int(col_offset))
+    # an index past the bank is a row without an adapter, as in the kernel
+    on = (row_adapter >= 0) & (row_adapter < n)
+    idx = row_adapter.clamp(0, n - 1).long()
+    t = torch.bmm(x, A[idx].transpose(1, 2))  # rounded to x's dtype
+    d = torch.bmm(t.float(), B[idx].float().transpose(1, 2))
+    ys = y[:, :, col_offset:col_offset + N]
+    new = (ys.float() + row_scale.view(-1, 1, 1) * d).to(y.dtype)
+    ys.copy_(torch.where(on.view(-1, 1, 1), new, ys))
+    return y

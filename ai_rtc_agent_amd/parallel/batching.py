@@ -24,6 +24,8 @@ from typing import Dict, List, Optional
 
 import torch
 
+from ..engine import LORA_KEEP
+
 
 class SlotProxy:
     """What a session holds: pipeline-shaped (callable + update surface)."""
@@ -52,6 +54,9 @@ class SlotProxy:
 
     def update_canny(self, low=None, high=None) -> None:
         self._owner.base.update_canny(low, high, slot=self.slot)
+
+    def update_lora(self, lora=LORA_KEEP, scale=None) -> None:
+        self._owner.base.update_lora(lora, scale, slot=self.slot)
 
     def stats(self) -> dict:
         return self._owner.stats()
@@ -93,6 +98,12 @@ class BatchedPipeline:
 
     def update_canny(self, low=None, high=None) -> None:
         self.base.update_canny(low, high)
+
+    def update_lora(self, lora=LORA_KEEP, scale=None) -> None:
+        self.base.update_lora(lora, scale)
+
+    def load_adapters(self, specs) -> None:
+        self.base.load_adapters(specs)
 
     # -- slot lifecycle --------------------------------------------------
     def acquire(self, stream_id: str) -> Optional[SlotProxy]:

@@ -18,7 +18,7 @@ from typing import Optional, Sequence
 import torch
 
 from .config import EngineConfig
-from .engine import StreamDiffusionEngine
+from .engine import LORA_KEEP, StreamDiffusionEngine
 
 
 class StreamDiffusionPipeline:
@@ -73,6 +73,21 @@ class StreamDiffusionPipeline:
     def update_canny(self, low: Optional[int] = None, high: Optional[int] = None,
                      slot: Optional[int] = None) -> None:
         self.engine.update_canny(low, high, slot=slot)
+
+    def update_lora(self, lora=LORA_KEEP, scale: Optional[float] = None,
+                    slot: Optional[int] = None) -> None:
+        """lora: a loaded adapter's name, None for no adapter, or LORA_KEEP
+        to change the scale alone (engine.update_lora)."""
+        self.engine.update_lora(adapter=lora, scale=scale, slot=slot)
+
+    def load_adapters(self, specs) -> None:
+        """Start-up: (name, path, scale) triples into bank indices 0, 1, ..."""
+        if len(specs) > self.cfg.lora_adapters:
+            raise ValueError(
+                f"{len(specs)} LoRA adapters named, the bank holds "
+                f"{self.cfg.lora_adapters} (--lora-adapters)")
+        for i, (name, path, scale) in enumerate(specs):
+            self.engine.load_adapter(i, path, scale=scale, name=name)
 
     def reset_slot(self, slot: int) -> None:
         self.engine.reset_slot(slot)

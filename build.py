@@ -21,7 +21,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from ai_rtc_agent_amd.config import EngineConfig
+from ai_rtc_agent_amd.config import EngineConfig, lora_adapter_specs
 from ai_rtc_agent_amd.engine import StreamDiffusionEngine
 from ai_rtc_agent_amd.engine.plan import save_plan
 
@@ -32,6 +32,9 @@ def build(
     lora: dict | None = None,
     width: int = 512,
     full_vae: bool = False,
+    lora_adapters: int | None = None,
+    lora_max_rank: int | None = None,
+    lora_adapter: list | None = None,
 ) -> str:
     cfg = EngineConfig(
         model_id=model_id,
@@ -46,8 +49,24 @@ def build(
         device="cuda" if torch.cuda.is_available() else "cpu",
         use_hip_graph=torch.cuda.is_available(),
     )
+    # per-session LoRA bank: the plan gets its own cache key, and the named
+    # adapter files are loaded once here so that a bad file fails the build,
+    # not the server's start-up
+    if lora_adapters is not None:
+        cfg.lora_adapters = lora_adapters
+    if lora_max_rank is not None:
+        cfg.lora_max_rank = lora_max_rank
+    cfg.__post_init__()
+    specs = lora_adapter_specs(lora_adapter)
+    if len(specs) > cfg.lora_adapters:
+        raise ValueError(
+            f"{len(specs)} LoRA adapters named, the bank holds "
+            f"{cfg.lora_adapters} (--lora-adapters)")
     eng = StreamDiffusionEngine(cfg)
     eng.prepare()
+    for i, (name, path, scale) in enumerate(specs):
+        counts = eng.load_adapter(i, path, scale=scale, name=name)
+        print(f"LoRA adapter {name!r} -> bank index {i}: {counts}")
     if torch.cuda.is_available():
         # warm the kernel-side weight transforms + capture the graph once
         frame = torch.zeros((width, width, 3), dtype=torch.uint8, device=cfg.device)
@@ -68,6 +87,14 @@ if __name__ == "__main__":
                    help="warm a plan with the checkpoint's full AutoencoderKL "
                         "(use_tiny_vae=False); it is cached beside the "
                         "tiny-VAE plan, under its own key")
+    p.add_argument("--lora-adapters", type=int, default=None,
+                   help="capacity of the per-session LoRA bank (0..64, "
+                        "default $AIRTC_LORA_ADAPTERS or 0 = off)")
+    p.add_argument("--lora-max-rank", type=int, default=None,
+                   help="largest adapter rank the bank accepts (1..64)")
+    p.add_argument("--lora-adapter", action="append", default=None,
+                   metavar="NAME=PATH[:SCALE]",
+                   help="check-load this adapter file into the bank; repeatable")
     a = p.parse_args()
     lora = None
     if a.lora:
@@ -75,4 +102,5 @@ if __name__ == "__main__":
         for item in a.lora.split(","):
             path, _, scale = item.partition(":")
             lora[path] = float(scale or 1.0)
-    build(a.model_id, a.family, lora, a.width, a.full_vae)
+    build(a.model_id, a.family, lora, a.width, a.full_vae,
+          a.lora_adapters, a.lora_max_rank, a.lora_adapter)

@@ -17,7 +17,7 @@ CSRC = os.path.join(ROOT, "ai_rtc_agent_amd", "ops", "csrc")
 
 sources = [
     os.path.join(CSRC, f)
-    for f in ["ext.cpp", "vcn.cpp", "h264sw.cpp", "dtls.cpp", "gemm_lt.cpp", "elementwise.hip", "color.hip", "canny.hip", "safety.hip", "norms.hip", "conv2d.hip", "attention.hip", "attention_wide.hip", "fp8.hip", "conv2d_fp8.hip"]
+    for f in ["ext.cpp", "vcn.cpp", "h264sw.cpp", "dtls.cpp", "gemm_lt.cpp", "elementwise.hip", "color.hip", "canny.hip", "safety.hip", "norms.hip", "conv2d.hip", "attention.hip", "attention_wide.hip", "lora.hip", "fp8.hip", "conv2d_fp8.hip"]
 ]
 
 setup(
